@@ -7,13 +7,16 @@ auto-resets finished games (config 3 of BASELINE.json, weights tdgammonNEW100k -
 explains why not bestModel.pth).  value = env steps (live-lane turns) of ALL ranks / wall time
 of the slowest rank, states resident in HBM.  The K timed steps are ONE bgamd_env_run_greedy(K)
 call (the same games as K step_greedy calls; consecutive steps share a launch); the dominant
-kernel is bracketed with HIP events on every 8th of those steps (every 4th in runs shorter than 80 steps; an event pair costs ~4 us).
+kernel is bracketed with HIP events on every 8th of those steps (every 4th in runs shorter than 80 steps; an event pair costs ~4 us) with --full.
 
     python bench.py [--gpus N --steps K --warmup W]            # N > 1: this process starts the N ranks itself (launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      # or a launcher does
+    python bench.py --dump-outputs DIR                         # also DIR/<name>.npy: the env after the last timed step (float32)
 
-After the timed region (outside the contract's bracket) the line also carries `training_round`: configs 4/5's per-GPU share -- self-play
-with the turn log + the TD(lambda) replay, with ONE all-reduce of the 25 601-float update per training step when there is more than one rank.
+A plain run sets up, warms up, times ONE region of exactly K steps and prints the line.  --full adds everything else, as extra information
+after the timed region: the kernel timing and roofline, the other value-net modes, the distinct-afterstate sample, the repetition of a region
+shorter than 10 ms (median of 15), the CPU baseline and `training_round`: configs 4/5's per-GPU share -- self-play with the turn log + the
+TD(lambda) replay, with ONE all-reduce of the 25 601-float update per training step when there is more than one rank.
 """
 import argparse
 import json
@@ -70,7 +73,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--training-round", dest="training_round", action="store_true", default=True,
-                    help="(default) extra object in the line, measured AFTER the timed region: one training round of configs 4/5's per-GPU "
+                    help="(default with --full) extra object in the line, measured AFTER the timed region: one training round of configs 4/5's per-GPU "
                          "share (self-play with the turn log + TD(lambda) replay; one all-reduce per training step when world > 1)")
     ap.add_argument("--no-training-round", dest="training_round", action="store_false",
                     help="skip it: its self-play launches the step's kernels on shrinking batches, and a rocprofv3 --stats summary "
@@ -80,7 +83,36 @@ def parse_args(argv=None):
                     "abandoned (the line is printed without it)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="--gpus N > 1 started plainly: seconds before the parent's watchdog "
                     "kills the ranks it started and reports")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline (see the module docstring); the --no-*, "
+                    "--training-round and --quick switches select among it.  Without it the run is the timed region and the line alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed region, write what its last step left per lane -- board, turn, "
+                    "dice, flags, chosen sequence and value -- as DIR/<name>.npy (float32; a fixed, seeded sample of the lanes past 60 MB)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 60_000_000             # the arrays of --dump-outputs: under 64 MB with the .npy headers
+
+
+def dump_outputs(env, out_dir, rank=0, world=1):
+    """What a caller of run_greedy holds after the timed region's last step: every lane's snapshot (state28 | turn | die1 | die2 | flags)
+    and last choice (chosen index, candidate count, sequence, its length, the value of the chosen afterstate), as float32 (the integers are
+    small: exact).  More lanes than fit in DUMP_LIMIT_BYTES (split among the ranks): a fixed, seeded sample of them, its lane indices in lanes.npy.
+    With more than one rank every rank writes its own shard as rank<r>_<name>.npy."""
+    torch.cuda.synchronize()
+    snap = env.snapshot().cpu().numpy()
+    lc = {k: v.cpu().numpy() for k, v in env.last_choice().items()}
+    arrays = {"states": snap[:, :28], "turns": snap[:, 28], "dice": snap[:, 29:31], "flags": snap[:, 31],
+              "chosen": lc["chosen"], "candidate_count": lc["count"], "chosen_seq": lc["seq"], "chosen_seq_len": lc["seq_len"],
+              "chosen_value": lc["value"]}
+    per_lane = sum(4 * (a.size // env.n) for a in arrays.values())
+    if env.n * per_lane > DUMP_LIMIT_BYTES // world:
+        keep = (DUMP_LIMIT_BYTES // world) // (per_lane + 4)                        # + 4 bytes per lane of lanes.npy
+        lanes = np.sort(np.random.RandomState(SEED).choice(env.n, keep, replace=False))
+        arrays = dict({k: a[lanes] for k, a in arrays.items()}, lanes=lanes)
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "rank%d_" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _free_port():
@@ -418,6 +450,8 @@ def main(argv=None):
     a = parse_args(argv)
     if a.quick:
         a.training_round = False
+    if not a.full:
+        a.training_round, a.no_cpu_baseline, a.no_kernel_timing = False, True, True
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -475,16 +509,19 @@ def main(argv=None):
             dist.barrier()                        # the closing barrier of the bracket: its own latency (an RCCL all-reduce + a host
         return dt                                 # round trip, ~0.4 ms of a 3 ms region) is not part of anybody's K steps
 
-    # A region shorter than 10 ms (the driver's --steps 20 is 3 ms) is at the mercy of one scheduling hiccup: it is
+    # --full: a region shorter than 10 ms (the driver's --steps 20 is 3 ms) is at the mercy of one scheduling hiccup: it is
     # then repeated -- every repetition is again EXACTLY a.steps steps between barrier + synchronize -- and the MEDIAN
-    # region is the one reported (all ranks take the same decision from rank 0's first region).
+    # region is the one reported (all ranks take the same decision from rank 0's first region).  A plain run times one region.
     regions = [timed_region()]
-    n_rep = torch.tensor([14 if regions[0] < 0.010 else 0], dtype=torch.int64, device=dev if a.dist_backend == "nccl" else "cpu")
-    if use_dist:
-        dist.broadcast(n_rep, src=0)
-    for _ in range(int(n_rep.item())):
-        regions.append(timed_region())
+    if a.full:
+        n_rep = torch.tensor([14 if regions[0] < 0.010 else 0], dtype=torch.int64, device=dev if a.dist_backend == "nccl" else "cpu")
+        if use_dist:
+            dist.broadcast(n_rep, src=0)
+        for _ in range(int(n_rep.item())):
+            regions.append(timed_region())
     elapsed = sorted(regions)[len(regions) // 2]
+    if a.dump_outputs:
+        dump_outputs(env, a.dump_outputs, rank, world)
 
     kt = env.kernel_times() if not a.no_kernel_timing else None
     env.time_kernels(False)
@@ -511,10 +548,10 @@ def main(argv=None):
     ranks_seen, per_rank_s = census(elapsed, device=cdev)      # how many ranks this process group really has, and each one's median region
     def build_line():
         """rank 0: everything of the line but the training round and the CPU baseline"""
-        u_step, c_step = distinct_ratio(env, prec, samples=1 if a.quick else 4)
+        u_step, c_step = distinct_ratio(env, prec, samples=1 if a.quick else 4) if a.full else (None, None)
         # the other value-net modes on the same env (untimed region of the contract: extra information only)
         alt = {}
-        if world == 1 and not a.quick:
+        if world == 1 and a.full and not a.quick:
             for name, pm in (("f32", bg.F32), ("f32_dense", bg.F32_DENSE), ("f16x2", bg.F16X2), ("bf16", bg.BF16)):
                 if name == a.precision:
                     continue
@@ -536,7 +573,8 @@ def main(argv=None):
             "config": {"workload": "config3: 65 536 concurrent games per MI355X, greedy 198->128->1 value net "
                                    "(tdgammonNEW100k weights), auto-reset, Philox dice",
                        "games_per_gpu": a.games, "burnin_steps": a.burnin, "parallelism": f"shard{world}",
-                       "raw_candidates_per_step": round(c_step, 2), "distinct_afterstates_per_step": round(u_step, 2),
+                       "raw_candidates_per_step": round(c_step, 2) if a.full else None,
+                       "distinct_afterstates_per_step": round(u_step, 2) if a.full else None,
                        "staged_leaves_per_step": round(tot["candidates_raw"] / max(tot["steps"], 1), 2),
                        "rows_evaluated_per_step": round(tot["rows_evaluated"] / max(tot["steps"], 1), 2),
                        "games_finished": tot["games_finished"]},

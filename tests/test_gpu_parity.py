@@ -660,12 +660,12 @@ def test_errors_are_loud(bg, weights):
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the contract fields (metric/value/unit/..., roofline, cpu_baseline)."""
+    """bench.py --full prints ONE JSON line with the contract fields (metric/value/unit/..., roofline, cpu_baseline)."""
     import json
     import subprocess
     import sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--burnin", "20",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--burnin", "20",
                           "--games", "8192"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -691,6 +691,48 @@ def test_bench_contract_line():
     assert c["host"]["cpu_model"] and c["host"]["nproc"] >= 1
     ac = c["all_cores"]
     assert ac["cores"] == c["host"]["usable_cores"] and ac["value"] > 0 and ac["kind"] == "port"
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the contract fields and nothing measured beside them, ONE region of exactly --steps steps (every lane is
+    live under auto-reset, so value x ms_per_step = the games); --dump-outputs writes the env after the last timed step as float32 arrays
+    that are legal positions and identical from run to run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    games, steps = 8192, 8
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "2", "--burnin", "20",
+                              "--games", str(games), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    for k in ("roofline", "kernels", "alt_modes", "training_round", "cpu_baseline"):
+        assert k not in d, k
+    assert d["steps"] == steps and d["timed_regions"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["ms_per_step"] * steps - d["region_ms"]["median"]) < 1e-2
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - games) < 1e-3 * games
+    shapes = {"states": (games, 28), "turns": (games,), "dice": (games, 2), "flags": (games,), "chosen": (games,), "candidate_count": (games,),
+              "chosen_seq": (games, 4, 2), "chosen_seq_len": (games,), "chosen_value": (games,)}
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert {k: v.shape for k, v in a.items()} == shapes and all(v.dtype == np.float32 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    st = a["states"]
+    assert (np.clip(st[:, :24], 0, None).sum(1) + st[:, 24] + st[:, 26] == 15).all()       # 15 checkers a side: board, bar, borne off
+    assert (np.clip(-st[:, :24], 0, None).sum(1) + st[:, 25] + st[:, 27] == 15).all()
+    assert ((a["dice"] >= 1) & (a["dice"] <= 6)).all() and np.isin(a["turns"], (0, 1)).all()
+    moved = a["candidate_count"] > 0
+    assert moved.mean() > 0.5 and ((a["chosen_value"][moved] >= 0) & (a["chosen_value"][moved] <= 1)).all()
+    run(tmp_path / "b")
+    for k, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))), k
 
 
 def test_reset_lanes_by_mask(bg, O):

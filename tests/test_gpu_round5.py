@@ -40,12 +40,12 @@ def O():
 # ---- bench.py --gpus N, started plainly ---------------------------------------------------------------------
 
 def test_bench_started_plainly_with_two_ranks():
-    """`python bench.py --gpus 2 --dist-backend gloo --games 32768 --steps 20 --warmup 5`, no launcher, no WORLD_SIZE: the parent starts the
+    """`python bench.py --full --gpus 2 --dist-backend gloo --games 32768 --steps 20 --warmup 5`, no launcher, no WORLD_SIZE: the parent starts the
     two ranks itself (before touching the GPU), relays rank 0's ONE line and the ranks' exit code.  The line says n_gpus 2, ranks_seen 2,
     counts both ranks' env steps, carries per-rank times and the training round (per-step all-reduce over both ranks; replicas identical)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--games", "32768",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--games", "32768",
                           "--steps", "20", "--warmup", "5", "--training-round-timeout", "600"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -80,7 +80,7 @@ def test_bench_rccl_route_rehearsed_on_one_rank():
         port = sk.getsockname()[1]
     env = dict(os.environ, BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--games", "16384", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--games", "16384", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

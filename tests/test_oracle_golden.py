@@ -242,39 +242,54 @@ def test_g5_greedy_trajectories(golden_dir, weights):
     assert n_checked > 0.9 * len(rows)
 
 
-def test_oracle_vs_compiled_reference_on_arbitrary_boards():
+def test_oracle_vs_compiled_reference_on_arbitrary_boards(golden_dir):
     """Positions that play never reaches (random placement, heavy stacks, late bear-off boards): the oracle
-    against the UNMODIFIED reference compiled into oracle/_ref -- runs wherever that module is present (the
+    against the UNMODIFIED reference -- its answers on these boards are fixture G10 (tests/golden/make_golden_g10.py,
+    from the reference compiled into oracle/_ref), and wherever that module is present it is asked as well (the
     binding cannot set bar counts, so those stay 0 here; bar positions are pinned by G1/G3)."""
     import importlib.util
     import sys
     from helpers import random_boards
+    g10 = np.load(os.path.join(golden_dir, "g10_arbitrary_boards.npz"))
+    seq_off = np.concatenate([[0], np.cumsum(g10["n_seq"])])
+    mv_off = np.concatenate([[0], np.cumsum(g10["n_moves"].ravel())])
     ref_dir = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref")
     so = [f for f in os.listdir(ref_dir)] if os.path.isdir(ref_dir) else []
     so = [f for f in so if f.startswith("backgammon_env") and f.endswith(".so")]
-    if not so:
-        pytest.skip("oracle/_ref not built here")
-    spec = importlib.util.spec_from_file_location("backgammon_env", os.path.join(ref_dir, so[0]))
-    saved = sys.modules.pop("backgammon_env", None)
-    try:
-        rb = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(rb)
-    finally:
-        if saved is not None:
-            sys.modules["backgammon_env"] = saved
-    p1, p2 = rb.Player("a", rb.PlayerType.PLAYER1), rb.Player("b", rb.PlayerType.PLAYER2)
+    rb = None
+    if so:
+        spec = importlib.util.spec_from_file_location("backgammon_env", os.path.join(ref_dir, so[0]))
+        saved = sys.modules.pop("backgammon_env", None)
+        try:
+            rb = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(rb)
+        finally:
+            if saved is not None:
+                sys.modules["backgammon_env"] = saved
+        p1, p2 = rb.Player("a", rb.PlayerType.PLAYER1), rb.Player("b", rb.PlayerType.PLAYER2)
     st = random_boards(1500, 7, with_bar=False)
+    assert (st == g10["boards"]).all()
     rng = np.random.RandomState(8)
     for i in range(len(st)):
+        pl, d1, d2 = int(rng.randint(2)), int(rng.randint(1, 7)), int(rng.randint(1, 7))
+        if i % 5 == 0:
+            d2 = d1
+        assert g10["dice"][i].tolist() == [pl, d1, d2]
+        q, ln, a = O.evaluate_turn_sequences(O.State.from28(st[i], pl), pl, d1, d2)
+        r = slice(seq_off[i], seq_off[i + 1])
+        ref_seqs = [[(int(o), int(d)) for o, d in x[:n]] for x, n in zip(g10["seqs"][r], g10["seq_len"][r])]
+        assert ref_seqs == O.sequences_as_lists(q, ln), (i, st[i].tolist(), pl, d1, d2)
+        assert g10["states"][r].shape == a.shape and (g10["states"][r] == a).all()
+        for k, die in enumerate(g10["dies"].tolist()):
+            j = i * len(g10["dies"]) + k
+            assert [(int(o), int(d)) for o, d in g10["moves"][mv_off[j]:mv_off[j + 1]]] == O.legal_moves(O.State.from28(st[i], pl), pl, die)
+        if rb is None:
+            continue
         g = rb.Game(0)
         g.setPlayers(p1, p2)
         g.setGameBoard([int(v) for v in st[i, :24]])
         g.setBorneOffPieces(0, int(st[i, 26])); g.setBorneOffPieces(1, int(st[i, 27]))
-        pl, d1, d2 = int(rng.randint(2)), int(rng.randint(1, 7)), int(rng.randint(1, 7))
-        if i % 5 == 0:
-            d2 = d1
         seqs, states = g.evaluateTurnSequences(pl, d1, d2)
-        q, ln, a = O.evaluate_turn_sequences(O.State.from28(st[i], pl), pl, d1, d2)
         assert [list(map(tuple, x)) for x in seqs] == O.sequences_as_lists(q, ln), (i, st[i].tolist(), pl, d1, d2)
         assert states.shape == a.shape and (states == a).all()
         for die in (1, 4, 6):

@@ -194,3 +194,48 @@ def test_bench_main_routes_gpus_n_to_the_launcher(monkeypatch):
     assert "WORLD_SIZE=3" in str(e.value.code)
     a = bench.parse_args([])
     assert a.gpus == 1 and a.training_round and not bench.parse_args(["--no-training-round"]).training_round
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+class _FakeEnv:
+    """The two getters dump_outputs reads, on the host: lane g holds g in every field."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def snapshot(self):
+        return torch.arange(self.n, dtype=torch.int32)[:, None].repeat(1, 32)
+
+    def last_choice(self):
+        g = torch.arange(self.n, dtype=torch.int32)
+        return {"chosen": g, "count": g, "seq": g[:, None, None].repeat(1, 4, 2).to(torch.int8), "seq_len": g, "value": g.float()}
+
+
+def test_bench_dump_outputs_names_and_the_lane_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float32 under DIR/<name>.npy; past the byte limit a seeded sample of lanes (the same every run),
+    listed in lanes.npy; with more than one rank each writes rank<r>_<name>.npy within its share of the limit."""
+    bench = _bench()
+    monkeypatch.setattr(bench, "np", np)
+    monkeypatch.setattr(bench, "torch", torch)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    names = {"states", "turns", "dice", "flags", "chosen", "candidate_count", "chosen_seq", "chosen_seq_len", "chosen_value"}
+    bench.dump_outputs(_FakeEnv(100), str(tmp_path / "all"))
+    a = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(a) == names and all(v.dtype == np.float32 and len(v) == 100 for v in a.values())
+    assert a["states"].shape == (100, 28) and a["dice"].shape == (100, 2) and a["chosen_seq"].shape == (100, 4, 2)
+    assert (a["states"] == np.arange(100)[:, None]).all() and (a["chosen_value"] == np.arange(100)).all()
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 50 * 176)          # 176 bytes per lane, 4 more for its index: room for 48 lanes
+    for d in ("s1", "s2"):
+        bench.dump_outputs(_FakeEnv(100), str(tmp_path / d))
+    s = {p.stem: np.load(p) for p in (tmp_path / "s1").iterdir()}
+    assert set(s) == names | {"lanes"} and sum(v.nbytes for v in s.values()) <= 50 * 176
+    lanes = s["lanes"]
+    assert len(lanes) == 48 and (np.diff(lanes) > 0).all() and (s["states"] == lanes[:, None]).all() and (s["turns"] == lanes).all()
+    assert all(np.array_equal(v, np.load(tmp_path / "s2" / (k + ".npy"))) for k, v in s.items())
+
+    bench.dump_outputs(_FakeEnv(100), str(tmp_path / "r"), rank=1, world=2)
+    r = {p.stem: np.load(p) for p in (tmp_path / "r").iterdir()}
+    assert set(r) == {"rank1_" + k for k in names | {"lanes"}} and len(r["rank1_lanes"]) == 24

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of environment switches on ONE GPU box: runs `bench.py --quick` once per variant, interleaved `--rounds` times so that
+"""A/B of environment switches on ONE GPU box: runs `bench.py --full --quick` once per variant, interleaved `--rounds` times so that
 clock / thermal drift hits every variant alike, and prints per variant the median ms per step and the per-kernel times.
     python tools/ab_env.py "BGAMD_EXPAND_MERGED=0" "BGAMD_EXPAND_MERGED=1" "BGAMD_EXPAND_MERGED=1 BGAMD_EXPAND_DBL_PCT=40" [--rounds 3] [--extra "--games 32768"]
 A variant is a space-separated list of NAME=VALUE (an empty string = the defaults)."""
@@ -24,7 +24,7 @@ for r in range(a.rounds):
         for kv in v.split():
             k, _, val = kv.partition("=")
             env[k] = val
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--quick", "--steps", str(a.steps)] + a.extra.split(),
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--quick", "--steps", str(a.steps)] + a.extra.split(),
                              env=env, capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B on ONE GPU box: runs bench.py --quick once per variant library (tools/ab_build.sh), interleaved `--rounds` times so
+"""A/B on ONE GPU box: runs bench.py --full --quick once per variant library (tools/ab_build.sh), interleaved `--rounds` times so
 that clock / thermal drift hits every variant alike, and prints per variant the median ms per step and per-kernel times.
     python tools/ab_run.py base v1 v2 [--rounds 3] [--steps 200] [--extra "--games 65536"]"""
 import argparse
@@ -21,7 +21,7 @@ for r in range(a.rounds):
     for n in a.names:
         lib = os.path.join(ROOT, "backgammon-engine_amd", "variants", f"libbgamd_{n}.so")
         env = dict(os.environ, BGAMD_LIB=lib)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--quick", "--steps", str(a.steps)] + a.extra.split(),
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--quick", "--steps", str(a.steps)] + a.extra.split(),
                              env=env, capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

@@ -7,8 +7,8 @@ TAG=${1:?tag}; KERNEL=${2:?kernel name substring}; shift 2
 OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 python3 -c "import __graft_entry__ as g; g.build()" > /dev/null
 export BGAMD_NO_BUILD=1
-rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT/a" -- python3 ${SQ_CMD:-bench.py --quick --steps 20 --burnin 100} "$@" > "$OUT/a.log" 2>&1
-rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$OUT/b" -- python3 ${SQ_CMD:-bench.py --quick --steps 20 --burnin 100} "$@" > "$OUT/b.log" 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT/a" -- python3 ${SQ_CMD:-bench.py --full --quick --steps 20 --burnin 100} "$@" > "$OUT/a.log" 2>&1
+rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$OUT/b" -- python3 ${SQ_CMD:-bench.py --full --quick --steps 20 --burnin 100} "$@" > "$OUT/b.log" 2>&1
 python3 - "$OUT" "$KERNEL" <<'PY'
 import csv, glob, sys, collections
 out, key = sys.argv[1], sys.argv[2]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-MODE kernel statistics and the step timeline at the headline size, from the kernel trace of the DEFAULT bench command
-(VERDICT r4 item 6).  `rocprofv3 --kernel-trace --stats -- python3 bench.py` averages a kernel over every launch of the process:
+"""Per-MODE kernel statistics and the step timeline at the headline size, from the kernel trace of the `--full` bench command
+(VERDICT r4 item 6).  `rocprofv3 --kernel-trace --stats -- python3 bench.py --full` averages a kernel over every launch of the process:
 expand_all_kernel over the steps of all four value-net modes, the value net over burn-in + timed launches.  This tool reads the same
 run's per-dispatch trace (*_kernel_trace.csv) and
   * groups the dispatches into env steps (expansion -> value net -> boundary / apply) and labels every step by its value-net kernel;
