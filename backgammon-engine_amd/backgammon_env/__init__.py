@@ -259,6 +259,28 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_run_greedy(self._h, self._flags(roll, auto_reset, False, only_player, slot),
                                                    float(epsilon), int(precision), int(n_steps), _stream()), "run_greedy")
 
+    def step_search(self, top_k=8, roll=True, auto_reset=True, no_flip=False, want_index=False, only_player=None, slot=0):
+        """One 2-ply expectimax turn (include/bgamd.h, bgamd_env_step_search): the top_k best afterstates by the net (0 = all
+        distinct ones) are re-scored by the average over the opponent's 21 rolls of the opponent's greedy reply, and the best of
+        them is played.  last_choice()["value"] is that 2-ply value; search_candidates() lists the kept candidates."""
+        _capi.check(self._lib.bgamd_env_step_search(self._h, self._flags(roll, auto_reset, no_flip, only_player, slot) |
+                                                    (WANT_INDEX if want_index else 0), int(top_k), _stream()), "step_search")
+        self._search_k = int(top_k)
+
+    def search_candidates(self):
+        """The last search step's kept candidates, best 1-ply value first: (states[n,K,28], v1[n,K], v2[n,K], kept[n]); K is
+        that step's top_k, or (top_k = 0) the largest kept count.  Slots past a lane's count are zero."""
+        kept = self._buf((self.n,), torch.int32)
+        _capi.check(self._lib.bgamd_env_search_read(self._h, None, None, None, _ptr(kept), _stream()), "search_read")
+        K = getattr(self, "_search_k", 0)
+        if K == 0:
+            K = int(kept.max().item()) if self.n else 0
+        st = self._buf((self.n, K, 28), torch.int32)
+        v1, v2 = self._buf((self.n, K), torch.float32), self._buf((self.n, K), torch.float32)
+        if K > 0:
+            _capi.check(self._lib.bgamd_env_search_read(self._h, _ptr(st), _ptr(v1), _ptr(v2), None, _stream()), "search_read")
+        return st, v1, v2, kept
+
     def last_choice(self):
         ch, cnt = self._buf((self.n,), torch.int32), self._buf((self.n,), torch.int32)
         sq, ln = self._buf((self.n, 4, 2), torch.int8), self._buf((self.n,), torch.int32)

@@ -57,6 +57,8 @@ SYMBOLS = [
     ("bgamd_env_step_greedy", C.c_int, [_P, C.c_int, C.c_float, C.c_int, _P]),
     ("bgamd_env_run_greedy", C.c_int, [_P, C.c_int, C.c_float, C.c_int, C.c_int64, _P]),
     ("bgamd_env_last_choice", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("bgamd_env_step_search", C.c_int, [_P, C.c_int, C.c_int, _P]),
+    ("bgamd_env_search_read", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("bgamd_env_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("bgamd_env_reset_stats", C.c_int, [_P, _P]),
     ("bgamd_env_try_move", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),

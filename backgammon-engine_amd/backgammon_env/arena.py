@@ -10,7 +10,7 @@ from . import F32, VecGame
 
 
 def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
-    """policies: ("net", slot) or ("random",).  The constructor seats the first mover by game parity
+    """policies: ("net", slot), ("search", slot, top_k) or ("random",).  The constructor seats the first mover by game parity
     (`Game(i % 2)`, train.py:265), no opening roll."""
     env.reset()
     env.set_states(None, torch.arange(env.n, dtype=torch.int32) % 2)
@@ -18,6 +18,8 @@ def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
         for player, pol in ((0, p1_policy), (1, p2_policy)):
             if pol[0] == "net":
                 env.step_greedy(auto_reset=False, only_player=player, slot=pol[1], precision=precision)
+            elif pol[0] == "search":
+                env.step_search(top_k=pol[2], auto_reset=False, only_player=player, slot=pol[1])
             else:
                 env.step_random(auto_reset=False, only_player=player)
         if t % 16 == 15 and bool(((env.flags() & 4) != 0).all()):
@@ -28,16 +30,23 @@ def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
     return int(done.sum()), int(p1_won.sum())
 
 
-def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000, precision=F32):
+def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000, precision=F32, plies_a: int = 1, plies_b: int = 1,
+                 top_k: int = 8):
     """Win rate of A vs B (B = None: a uniformly random mover), sides alternated 50/50 as in
     evaluate_parallel (train.py:296-302): every lane plays one game with A as PLAYER1 and one with A as
-    PLAYER2.  -> dict(games, a_wins, win_rate)."""
+    PLAYER2.  plies_a / plies_b = 2: that side moves by the 2-ply search (VecGame.step_search, top_k candidates, fp32 net).
+    -> dict(games, a_wins, win_rate)."""
+    if plies_a not in (1, 2) or plies_b not in (1, 2):
+        raise ValueError("plies must be 1 or 2")
+    if plies_b == 2 and weights_b is None:
+        raise ValueError("a random mover does not search")
     env.load_weights(weights_a, slot=0)
     if weights_b is not None:
         env.load_weights(weights_b, slot=1)
-    b = ("net", 1) if weights_b is not None else ("random",)
-    n1, w1 = _play(env, ("net", 0), b, max_turns, precision)          # A is PLAYER1
-    n2, w2 = _play(env, b, ("net", 0), max_turns, precision)          # A is PLAYER2
+    a = ("net", 0) if plies_a == 1 else ("search", 0, top_k)
+    b = (("net", 1) if plies_b == 1 else ("search", 1, top_k)) if weights_b is not None else ("random",)
+    n1, w1 = _play(env, a, b, max_turns, precision)          # A is PLAYER1
+    n2, w2 = _play(env, b, a, max_turns, precision)          # A is PLAYER2
     a_wins = w1 + (n2 - w2)
     return {"games": n1 + n2, "a_wins": a_wins, "win_rate": a_wins / max(n1 + n2, 1),
             "a_as_p1": (n1, w1), "a_as_p2": (n2, n2 - w2)}

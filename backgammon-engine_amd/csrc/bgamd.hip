@@ -632,6 +632,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 
 #include "bg_staged_kernels.h"
 #include "bg_random_kernels.h"
+#include "bg_search.h"
 
 }  // namespace
 
@@ -715,6 +716,18 @@ struct bgamd_env {
     size_t ev_used = 0;
     double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // 2-ply search (bgamd_env_step_search, bg_search.h).  scratch: the env whose lanes are the virtual roots of a chunk, created on
+    // first use and grown up to SEARCH_CHUNK lanes; it borrows this env's weight tables (borrows_weights: not its to free)
+    bgamd_env *scratch = nullptr;
+    bool borrows_weights = false;
+    uint32_t *s_cnt = nullptr, *s_off = nullptr, *s_fill = nullptr, *s_kept = nullptr, *s_koff = nullptr, *s_max = nullptr;  // per game (+1)
+    uint32_t *s_grp = nullptr;             // [cap_rows] row indices grouped by game
+    int32_t *s_rank = nullptr;             // [cap_rows]
+    uint4 *c_rows = nullptr;               // candidates [c_cap][2]
+    uint32_t *c_key = nullptr;
+    float *c_v1 = nullptr, *c_v2 = nullptr, *c_rval = nullptr;     // c_rval [c_cap][21]
+    long long c_cap = 0;
+    int search_k = -1;                     // K of the last search step (-1: none yet)
 };
 
 namespace {
@@ -800,8 +813,18 @@ int bgamd_device_count(void)
 static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
                         int64_t arena_rows);
 
+static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
+                      int64_t arena_rows, bool borrows_weights);
+
 int bgamd_env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed, uint64_t lane_offset,
                      uint64_t lane_stride, int64_t arena_rows)
+{
+    return env_create(out, n_games, device, seed, lane_offset, lane_stride, arena_rows, false);
+}
+
+// borrows_weights: the search's scratch env -- no weight tables of its own, the parent's are pointed at before every use
+static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
+                      int64_t arena_rows, bool borrows_weights)
 {
     if (!out || n_games <= 0 || n_games > (1ll << 30)) return BGAMD_E_INVALID;
     int ndev = 0;
@@ -813,6 +836,7 @@ int bgamd_env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed
     bgamd_env *env = new bgamd_env();
     env->device = device;
     env->n_cu = prop.multiProcessorCount;
+    env->borrows_weights = borrows_weights;
     int rc = env_allocate(env, n_games, seed, lane_offset, lane_stride, arena_rows);
     if (rc == BGAMD_OK) rc = bgamd_env_reset(env, nullptr);
     if (rc != BGAMD_OK) {                       // free whatever was allocated before the failure
@@ -895,7 +919,7 @@ static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t
     HIPCHK(hipMalloc(&v.seqs, (size_t)cap * 4));
     HIPCHK(hipMalloc(&v.values, (size_t)cap * 4));
     HIPCHK(hipMalloc(&v.counters, C_COUNT * 8));
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 2 && !env->borrows_weights; ++k) {
         HIPCHK(hipMalloc(&env->d_w[k], N_PARAMS * 4));
         HIPCHK(hipMalloc(&env->d_wl[k], EVAL_LDS_BYTES));
         HIPCHK(hipMalloc(&env->d_wt[k], DELTA_W_FLOATS * 4));
@@ -910,9 +934,9 @@ static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t
         HIPCHK(hipMalloc(&env->d_wd16[k], EVAL16X2_W_BYTES));
 #endif
     }
-    HIPCHK(hipMalloc(&env->d_lut16, EVAL16_LUT_BYTES));
+    if (!env->borrows_weights) HIPCHK(hipMalloc(&env->d_lut16, EVAL16_LUT_BYTES));
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_f16x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL16X2_LDS_TOTAL));
-    HIPCHK(hipMalloc(&env->d_lut, EVAL16_LUT_BYTES));
+    if (!env->borrows_weights) HIPCHK(hipMalloc(&env->d_lut, EVAL16_LUT_BYTES));
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL16_LDS_TOTAL));
     {   // staged greedy step (bg_staged.h): node lists, per-workgroup staging, unique arena
         StagedView &sv = env->sv;
@@ -966,6 +990,20 @@ int bgamd_env_destroy(bgamd_env *env)
 {
     ENV_GUARD(env);
     hipDeviceSynchronize();
+    if (env->scratch) bgamd_env_destroy(env->scratch);
+    HIPCHK(hipSetDevice(env->device));
+    if (env->borrows_weights) {                  // the parent's tables: not ours to free
+        for (int k = 0; k < 2; ++k) {
+            env->d_w[k] = nullptr; env->d_wl[k] = nullptr; env->d_wt[k] = nullptr; env->d_wm[k] = nullptr; env->d_wl3[k] = nullptr;
+            env->d_wr2[k] = nullptr; env->d_wl16[k] = nullptr; env->d_wlx2[k] = nullptr; env->d_wd16[k] = nullptr;
+        }
+        env->d_lut = nullptr; env->d_lut16 = nullptr;
+    }
+    {
+        void *sp[] = {env->s_cnt, env->s_off, env->s_fill, env->s_kept, env->s_koff, env->s_max, env->s_grp, env->s_rank, env->c_rows,
+                      env->c_key, env->c_v1, env->c_v2, env->c_rval};
+        for (void *p : sp) if (p) hipFree(p);
+    }
     EnvView &v = env->v;
     void *ptrs[] = {v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq,
                     v.chosen_val, v.rows, v.seqs, v.values, v.counters, env->d_w[0], env->d_wl[0], env->d_wl16[0], env->d_w[1], env->d_wl[1], env->d_wl16[1], env->d_lut, env->d_wlx2[0], env->d_wlx2[1], env->d_wd16[0], env->d_wd16[1], env->d_lut16, env->d_wt[0], env->d_wt[1], env->d_wm[0], env->d_wm[1], env->d_wl3[0], env->d_wl3[1], env->d_wr2[0], env->d_wr2[1], env->sv.root_rows, env->sv.root_hidden,
@@ -1473,7 +1511,8 @@ struct GreedyRun {
         hipLaunchKernelGGL(roots_kernel, grid1(env->v.n, LANE_NT), dim3(LANE_NT), 0, s, ev, sv, flags);
         return BGAMD_OK;
     }
-    int step(const StepStreams &ss, bool more, bool first_of_run = true)
+    // score_only (the 2-ply search, bg_search.h): roots, expansion and value net only -- no apply launch, sv.best is left for the caller
+    int step(const StepStreams &ss, bool more, bool first_of_run = true, bool score_only = false)
     {
         (void)first_of_run;
         const long long n = env->v.n;
@@ -1584,7 +1623,7 @@ struct GreedyRun {
             const long long lim = (long long)ss.n_cu * 8;
             hipLaunchKernelGGL(rnd_count_kernel, dim3((unsigned)(b > lim ? lim : b)), dim3(256), 0, s, ev, env->rv);
         }
-        {
+        if (!score_only) {
             KTimer t(env, s, 2);
             ev.end_slot = ev.traj_ring ? cur_step % ev.traj_ring : 0;      // the apply half closes the step the last roots began
             if (fused) {
@@ -1644,6 +1683,148 @@ int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision
 int bgamd_env_step_greedy(bgamd_env *env, int flags, float epsilon, int precision, void *stream)
 {
     return bgamd_env_run_greedy(env, flags, epsilon, precision, 1, stream);
+}
+
+// ---- 2-ply expectimax (bg_search.h) ---------------------------------------------------------------------------------------
+// Virtual lanes per pass of stage C: the scratch env has at most this many lanes (a 131 072-lane env: ~3.4 GB).  Every virtual
+// lane is scored on its own, so no result depends on it.
+constexpr long long SEARCH_CHUNK = 131072;
+
+static int search_grow(bgamd_env *env, long long need)
+{
+    if (need <= env->c_cap) return BGAMD_OK;
+    void *old[] = {env->c_rows, env->c_key, env->c_v1, env->c_v2, env->c_rval};
+    for (void *p : old) if (p) HIPCHK(hipFree(p));
+    env->c_rows = nullptr; env->c_key = nullptr; env->c_v1 = env->c_v2 = env->c_rval = nullptr; env->c_cap = 0;
+    const long long cap = need < 1024 ? 1024 : need;
+    HIPCHK(hipMalloc(&env->c_rows, (size_t)cap * 32));
+    HIPCHK(hipMalloc(&env->c_key, (size_t)cap * 4));
+    HIPCHK(hipMalloc(&env->c_v1, (size_t)cap * 4));
+    HIPCHK(hipMalloc(&env->c_v2, (size_t)cap * 4));
+    HIPCHK(hipMalloc(&env->c_rval, (size_t)cap * SRCH_ROLLS * 4));
+    env->c_cap = cap;
+    return BGAMD_OK;
+}
+
+int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
+{
+    if (!env || top_k < 0) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = env->v.n;
+    GreedyRun run;
+    int rc = run.init(env, flags, 0.0f, BGAMD_F32);
+    if (rc) return rc;
+    if (!env->s_cnt) {
+        uint32_t **per_game[] = {&env->s_cnt, &env->s_off, &env->s_fill, &env->s_kept, &env->s_koff};
+        for (uint32_t **p : per_game) HIPCHK(hipMalloc(p, (size_t)(n + 1) * 4));
+        HIPCHK(hipMalloc(&env->s_max, 8));
+        HIPCHK(hipMalloc(&env->s_grp, (size_t)env->sv.cap_rows * 4));
+        HIPCHK(hipMalloc(&env->s_rank, (size_t)env->sv.cap_rows * 4));
+    }
+    long long n_cand = top_k > 0 ? n * (long long)top_k : 0;         // bound on the kept candidates (top_k = 0: read back below)
+    if (top_k > 0 && (rc = search_grow(env, n_cand))) return rc;
+    env->search_k = -1;
+
+    // stage A: the greedy step's roots, expansion and incremental value net, no apply
+    const StepStreams ss{s, s, env->n_cu};
+    if ((rc = run.begin(s)) || (rc = run.step(ss, false, true, true))) return rc;
+
+    // stage B: group by game, select, list the kept candidates
+    const unsigned long long *tops = env->sv.tops;
+    const long long bb = env->sv.b_base, cap_rows = env->sv.cap_rows;
+    const uint2 *info = env->sv.u_info;
+    const uint4 *rows = env->sv.u_rows;
+    const dim3 rgrid((unsigned)(env->n_cu * 8));
+    HIPCHK(hipMemsetAsync(env->s_cnt, 0, (size_t)n * 4, s));
+    HIPCHK(hipMemsetAsync(env->s_fill, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(srch_count_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, env->s_cnt);
+    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)env->s_cnt, env->s_off, n, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(srch_scatter_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, (const uint32_t *)env->s_off, env->s_fill,
+                       env->s_grp);
+    const uint32_t k_lim = top_k > 0 ? (uint32_t)top_k : 0xFFFFFFFFu;
+    hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)env->s_cnt, (const uint32_t *)env->s_off,
+                       (const uint32_t *)env->s_grp, rows, info, (const float *)env->v.values, k_lim, env->s_rank, env->s_kept);
+    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)env->s_kept, env->s_koff, n, env->s_max);
+    int K = top_k;
+    if (top_k == 0) {                                  // every distinct afterstate: the list's length is read back (the one synchronisation)
+        uint32_t h[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(&h[0], env->s_koff + n, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h[1], env->s_max, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        n_cand = h[0]; K = (int)h[1];
+        if ((rc = search_grow(env, n_cand))) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(srch_emit_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint32_t *)env->s_cnt, (const uint32_t *)env->s_off,
+                       (const uint32_t *)env->s_grp, rows, info, (const float *)env->v.values, (const int32_t *)env->s_rank,
+                       (const uint32_t *)env->s_koff, env->c_rows, env->c_key, env->c_v1);
+
+    // stage C: one virtual lane per (candidate, opponent roll), SEARCH_CHUNK at a time through the scratch env
+    const int slot = run.slot;
+    const long long n_virtual = n_cand * SRCH_ROLLS;
+    if (n_virtual > 0) {
+        long long want = n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK;
+        if (env->scratch && env->scratch->v.n < want) {
+            HIPCHK(hipStreamSynchronize(s));
+            bgamd_env_destroy(env->scratch);
+            env->scratch = nullptr;
+        }
+        if (!env->scratch) {
+            bgamd_env *sc = nullptr;
+            if ((rc = env_create(&sc, want, env->device, 0, 0, 0, 0, true))) return rc;
+            HIPCHK(hipDeviceSynchronize());            // (its reset ran on the null stream)
+            env->scratch = sc;
+        }
+        HIPCHK(hipSetDevice(env->device));
+        bgamd_env *sc = env->scratch;
+        for (int k = 0; k < 2; ++k) {                  // the tables of this env as they are now: a reload is seen
+            sc->d_w[k] = env->d_w[k]; sc->d_wl[k] = env->d_wl[k]; sc->d_wt[k] = env->d_wt[k]; sc->d_wm[k] = env->d_wm[k];
+            sc->wm_ok[k] = env->wm_ok[k]; sc->d_wl3[k] = env->d_wl3[k]; sc->d_wr2[k] = env->d_wr2[k]; sc->d_wl16[k] = env->d_wl16[k];
+            sc->d_wlx2[k] = env->d_wlx2[k]; sc->d_wd16[k] = env->d_wd16[k]; sc->has_weights[k] = env->has_weights[k];
+        }
+        sc->d_lut = env->d_lut; sc->d_lut16 = env->d_lut16;
+        const float *w2 = env->d_w[slot] + N_HID * N_IN + N_HID, *b2 = w2 + N_HID;
+        const StepStreams sss{s, s, sc->n_cu};
+        for (long long v0 = 0; v0 < n_virtual; v0 += sc->v.n) {
+            hipLaunchKernelGGL(srch_fanout_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, v0,
+                               (const uint32_t *)(env->s_koff + n), (const uint4 *)env->c_rows, (const uint32_t *)env->c_key);
+            GreedyRun sr;
+            if ((rc = sr.init(sc, flags & BGAMD_WEIGHTS_SLOT1, 0.0f, BGAMD_F32)) || (rc = sr.begin(s)) ||
+                (rc = sr.step(sss, false, true, true)))
+                return rc;
+            hipLaunchKernelGGL(srch_collect_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, (const unsigned long long *)sc->sv.best,
+                               (const float *)sc->sv.root_hidden, w2, b2, v0, env->c_rval);
+        }
+    }
+
+    // stage D: V2, choice, and the greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice)
+    hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)env->s_kept,
+                       (const uint32_t *)env->s_koff, (const uint4 *)env->c_rows, (const uint32_t *)env->c_key, (const float *)env->c_v1,
+                       (const float *)env->c_rval, env->c_v2, env->sv.best, &env->v.counters[C_ERR],
+                       env->scratch ? &env->scratch->v.counters[C_ERR] : (unsigned long long *)nullptr);
+    const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
+    hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
+    HIPCHK(hipGetLastError());
+    env->search_k = K;
+    return BGAMD_OK;
+}
+
+int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream)
+{
+    ENV_GUARD(env);
+    if (env->search_k < 0) return BGAMD_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = env->v.n;
+    const int K = env->search_k;
+    if (d_kept) hipLaunchKernelGGL(srch_kept_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)env->s_kept, d_kept);
+    if (K > 0 && (d_states28 || d_v1 || d_v2))
+        hipLaunchKernelGGL(srch_read_kernel, grid1(n * K, SRCH_NT), dim3(SRCH_NT), 0, s, n, K, (const uint32_t *)env->s_kept,
+                           (const uint32_t *)env->s_koff, (const uint4 *)env->c_rows, (const float *)env->c_v1, (const float *)env->c_v2,
+                           d_states28, d_v1, d_v2);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
 }
 
 int bgamd_env_last_choice(bgamd_env *env, int32_t *d_chosen, int32_t *d_count, int8_t *d_seq, int32_t *d_seq_len,

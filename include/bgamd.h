@@ -186,6 +186,33 @@ int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision
 int bgamd_env_last_choice(bgamd_env *env, int32_t *d_chosen, int32_t *d_count, int8_t *d_seq /*[n,4,2]*/,
                           int32_t *d_seq_len, float *d_value, void *stream);
 
+/* ---- 2-ply expectimax move search (TD-Gammon's 2-ply) -------------------------------------------------------------------------
+ * One searched turn for every live lane that takes part (flags: BGAMD_ROLL, BGAMD_AUTO_RESET, BGAMD_NO_FLIP, BGAMD_WANT_INDEX,
+ * BGAMD_ONLY_P1/P2 and BGAMD_WEIGHTS_SLOT1 mean what they mean for the greedy step; no epsilon; the F32 incremental value net only):
+ *   1. roll and enumerate exactly as the greedy step does (same Philox stream, mover, weight slot);
+ *   2. v1(c) of every distinct afterstate c: the greedy step's value, bit for bit (mover's turn bit) -- except a TERMINAL c (the
+ *      mover has borne off the 15th checker), which scores its outcome exactly: 1.0 if PLAYER1 won, 0.0 if PLAYER2 won;
+ *   3. keep the top_k best by v1 for the mover (copies of one afterstate count once; ties: the smaller key = the earlier
+ *      reference-order index, the greedy step's rule); top_k = 0 keeps every distinct afterstate;
+ *   4. V2(c) = v1(c) for a terminal c; otherwise  V2(c) = sum over the 21 unordered opponent rolls r = (1,1), (1,2), ..., (6,6), in that
+ *      order, of w_r R(c, r), w_r = 1/36 for a double and 2/36 otherwise, where R(c, r) is the value of the reply the greedy step
+ *      would choose from c (the opponent's turn bit, arg-min for PLAYER2 / arg-max for PLAYER1, no special case for terminal
+ *      replies) -- or, when the opponent has no legal move, the net's value of c with the OPPONENT's turn bit;
+ *   5. choose the kept c with the best V2 for the mover (ties: the smaller key), then apply / terminal check / flip or auto-reset
+ *      exactly as the greedy step does;
+ *   6. bgamd_env_last_choice: the chosen sequence, index and count (exact with BGAMD_WANT_INDEX), value = V2 of the choice.
+ * Stream-ordered; with top_k > 0 the host never waits (n * top_k * 21 virtual roots are bounded up front, slots past a lane's kept
+ * count are skipped on the device); top_k = 0 reads the number of kept candidates back once.  The (candidate, roll) pairs are
+ * scored by the greedy step's own roots / expansion / value-net kernels on an internal scratch env (created on first use, grown up to
+ * a fixed chunk of lanes, freed by bgamd_env_destroy; it uses this env's weight tables).  A search step writes neither the
+ * trajectory log nor the ring log: with either set it returns BGAMD_E_INVALID.  Arena overflow, missing weights and delta errors
+ * surface as they do for the greedy step. */
+int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream);
+/* The last search step's kept candidates, best v1 first: d_states28 [n,K,28], d_v1 [n,K], d_v2 [n,K] (zero past a lane's count),
+ * d_kept [n].  K = the last call's top_k; with top_k = 0 the largest kept count.  Any pointer may be NULL.  BGAMD_E_INVALID before
+ * the first search step. */
+int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream);
+
 /* (slot 8 below counts the 32-row x 2-feature MFMA steps of the dense f32 net, or the W1 columns added by the
  * incremental one) */
 /* counters since create/reset_stats (synchronises): [steps, games_finished, p1_wins, candidates_raw,
