@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import (AUTO_RESET, BF16, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1, ONLY_P2, ROLL, WANT_INDEX, WEIGHTS_SLOT1,  # noqa: F401
-                    BgamdError)
+from ._capi import (AUTO_RESET, BF16, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1, ONLY_P2, ROLL, ROLLOUT_ROTATE, WANT_INDEX,  # noqa: F401
+                    WEIGHTS_SLOT1, BgamdError)
 
 __all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "BgamdError", "set_seed", "pack_rows"]
 
@@ -280,6 +280,34 @@ class VecGame:
         if K > 0:
             _capi.check(self._lib.bgamd_env_search_read(self._h, _ptr(st), _ptr(v1), _ptr(v2), None, _stream()), "search_read")
         return st, v1, v2, kept
+
+    def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
+                per_trial=False):
+        """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
+        move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
+        trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
+        env's weights (slot) are used; its own lanes are untouched.  -> dict of device tensors: mean [P] (float64, the share of PLAYER1
+        wins), stderr [P], turns [P] (int64), truncated [P] (int32); per_trial: also trial_value [P, T] (float32), trial_turns [P, T]."""
+        st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
+        P, T = st.shape[0], int(trials)
+        t = self._dev(turn, torch.int32, (P,))
+        out = {"mean": self._buf((P,), torch.float64), "stderr": self._buf((P,), torch.float64),
+               "turns": self._buf((P,), torch.int64), "truncated": self._buf((P,), torch.int32)}
+        if per_trial:
+            out["trial_value"] = self._buf((P, max(T, 0)), torch.float32)
+            out["trial_turns"] = self._buf((P, max(T, 0)), torch.int32)
+        flags = (ROLLOUT_ROTATE if rotate else 0) | (WEIGHTS_SLOT1 if slot else 0)
+        _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
+                                                int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
+                                                _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
+                                                _ptr(out.get("trial_turns")), _stream()), "rollout")
+        return out
+
+    def rollout_info(self):
+        """The last rollout's [lanes, env steps issued, lane-steps of live trials, turns per run]: idle share = 1 - [2] / ([0] [1])."""
+        h = (C.c_int64 * 4)()
+        _capi.check(self._lib.bgamd_env_rollout_info(self._h, h), "rollout_info")
+        return list(h)
 
     def last_choice(self):
         ch, cnt = self._buf((self.n,), torch.int32), self._buf((self.n,), torch.int32)

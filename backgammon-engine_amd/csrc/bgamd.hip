@@ -16,6 +16,8 @@
 #include <vector>
 #include <queue>
 #include <algorithm>
+#include <initializer_list>
+#include <utility>
 #include <dlfcn.h>
 #include <rccl/rccl.h>          // types and prototypes only: the library is resolved at run time (rccl_api below), libbgamd.so does not link it
 
@@ -633,6 +635,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 #include "bg_staged_kernels.h"
 #include "bg_random_kernels.h"
 #include "bg_search.h"
+#include "bg_rollout.h"
 
 }  // namespace
 
@@ -728,6 +731,15 @@ struct bgamd_env {
     float *c_v1 = nullptr, *c_v2 = nullptr, *c_rval = nullptr;     // c_rval [c_cap][21]
     long long c_cap = 0;
     int search_k = -1;                     // K of the last search step (-1: none yet)
+    // Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h).  rscratch: the env whose lanes play the trials, created on first use with
+    // the call's lane count (re-created when it differs); it borrows this env's weight tables as the search's scratch env does
+    bgamd_env *rscratch = nullptr;
+    uint4 *r_pos = nullptr, *r_fan = nullptr, *r_trows = nullptr;
+    float *r_fval = nullptr, *r_tval = nullptr, *r_tv = nullptr;
+    uint32_t *r_tturns = nullptr, *r_lane = nullptr, *r_tids = nullptr;
+    unsigned long long *r_ctr = nullptr, *r_host = nullptr;        // r_host: pinned, [2][2] (done, error bits) of the last two reads
+    long long r_cap_pos = 0, r_cap_fan = 0, r_cap_trials = 0, r_cap_lanes = 0;
+    int64_t r_info[4] = {0, 0, 0, 0};      // bgamd_env_rollout_info
 };
 
 namespace {
@@ -991,6 +1003,7 @@ int bgamd_env_destroy(bgamd_env *env)
     ENV_GUARD(env);
     hipDeviceSynchronize();
     if (env->scratch) bgamd_env_destroy(env->scratch);
+    if (env->rscratch) bgamd_env_destroy(env->rscratch);
     HIPCHK(hipSetDevice(env->device));
     if (env->borrows_weights) {                  // the parent's tables: not ours to free
         for (int k = 0; k < 2; ++k) {
@@ -1001,8 +1014,10 @@ int bgamd_env_destroy(bgamd_env *env)
     }
     {
         void *sp[] = {env->s_cnt, env->s_off, env->s_fill, env->s_kept, env->s_koff, env->s_max, env->s_grp, env->s_rank, env->c_rows,
-                      env->c_key, env->c_v1, env->c_v2, env->c_rval};
+                      env->c_key, env->c_v1, env->c_v2, env->c_rval, env->r_pos, env->r_fan, env->r_trows, env->r_fval, env->r_tval,
+                      env->r_tv, env->r_tturns, env->r_lane, env->r_tids, env->r_ctr};
         for (void *p : sp) if (p) hipFree(p);
+        if (env->r_host) hipHostFree(env->r_host);
     }
     EnvView &v = env->v;
     void *ptrs[] = {v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq,
@@ -1690,6 +1705,17 @@ int bgamd_env_step_greedy(bgamd_env *env, int flags, float epsilon, int precisio
 // lane is scored on its own, so no result depends on it.
 constexpr long long SEARCH_CHUNK = 131072;
 
+// a scratch env (borrows_weights) points at its parent's weight tables as they are now
+static void scratch_borrow(const bgamd_env *env, bgamd_env *sc)
+{
+    for (int k = 0; k < 2; ++k) {
+        sc->d_w[k] = env->d_w[k]; sc->d_wl[k] = env->d_wl[k]; sc->d_wt[k] = env->d_wt[k]; sc->d_wm[k] = env->d_wm[k];
+        sc->wm_ok[k] = env->wm_ok[k]; sc->d_wl3[k] = env->d_wl3[k]; sc->d_wr2[k] = env->d_wr2[k]; sc->d_wl16[k] = env->d_wl16[k];
+        sc->d_wlx2[k] = env->d_wlx2[k]; sc->d_wd16[k] = env->d_wd16[k]; sc->has_weights[k] = env->has_weights[k];
+    }
+    sc->d_lut = env->d_lut; sc->d_lut16 = env->d_lut16;
+}
+
 static int search_grow(bgamd_env *env, long long need)
 {
     if (need <= env->c_cap) return BGAMD_OK;
@@ -1779,12 +1805,7 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
         }
         HIPCHK(hipSetDevice(env->device));
         bgamd_env *sc = env->scratch;
-        for (int k = 0; k < 2; ++k) {                  // the tables of this env as they are now: a reload is seen
-            sc->d_w[k] = env->d_w[k]; sc->d_wl[k] = env->d_wl[k]; sc->d_wt[k] = env->d_wt[k]; sc->d_wm[k] = env->d_wm[k];
-            sc->wm_ok[k] = env->wm_ok[k]; sc->d_wl3[k] = env->d_wl3[k]; sc->d_wr2[k] = env->d_wr2[k]; sc->d_wl16[k] = env->d_wl16[k];
-            sc->d_wlx2[k] = env->d_wlx2[k]; sc->d_wd16[k] = env->d_wd16[k]; sc->has_weights[k] = env->has_weights[k];
-        }
-        sc->d_lut = env->d_lut; sc->d_lut16 = env->d_lut16;
+        scratch_borrow(env, sc);                       // the tables of this env as they are now: a reload is seen
         const float *w2 = env->d_w[slot] + N_HID * N_IN + N_HID, *b2 = w2 + N_HID;
         const StepStreams sss{s, s, sc->n_cu};
         for (long long v0 = 0; v0 < n_virtual; v0 += sc->v.n) {
@@ -1824,6 +1845,179 @@ int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, floa
                            (const uint32_t *)env->s_koff, (const uint4 *)env->c_rows, (const float *)env->c_v1, (const float *)env->c_v2,
                            d_states28, d_v1, d_v2);
     HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+// ---- Monte Carlo rollouts (bg_rollout.h) -----------------------------------------------------------------------------------
+// Default lanes of the scratch env that plays the trials (a 65 536-lane env: ~1.7 GB); fewer when the call has fewer trials.
+constexpr long long ROLLOUT_LANES = 65536;
+// Turns per run between two refill points (M > 0: the largest divisor of the turns a trial has left at its start not above it).  A trial
+// that ends inside a run leaves its lane idle for the rest of the run: R / 2 turns per trial on average, against ~83 per game.
+constexpr int ROLLOUT_RUN = 8;
+
+static int ro_grow(long long need, long long &cap, std::initializer_list<std::pair<void **, size_t>> bufs)
+{
+    if (need <= cap) return BGAMD_OK;
+    for (auto &b : bufs) { if (*b.first) HIPCHK(hipFree(*b.first)); *b.first = nullptr; }
+    cap = 0;
+    for (auto &b : bufs) HIPCHK(hipMalloc(b.first, (size_t)need * b.second));
+    cap = need;
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n_positions,
+                      int64_t position_offset, int64_t trials, int64_t max_plies, uint64_t seed, int64_t lanes,
+                      double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
+                      float *d_trial_value, int32_t *d_trial_turns, void *stream)
+{
+    if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
+    if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1)) return BGAMD_E_INVALID;
+    if (n_positions >= (1ll << 31) || trials >= (1ll << 31) || n_positions * trials >= (1ll << 31) || lanes > (1ll << 30))
+        return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    const int slot = (flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
+    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    hipStream_t s = (hipStream_t)stream;
+    const long long P = n_positions, T = trials, N = P * T, M = max_plies;
+    const bool rotate = (flags & BGAMD_ROLLOUT_ROTATE) != 0;
+    const long long F = rotate ? (T < 36 ? T : 36) : 0, n_fan = P * F;
+    const long long L = lanes > 0 ? lanes : (N < ROLLOUT_LANES ? ((N + 255) / 256) * 256 : ROLLOUT_LANES);
+    int rc;
+
+    // the scratch env and the buffers of this call
+    if (env->rscratch && env->rscratch->v.n != L) {
+        HIPCHK(hipStreamSynchronize(s));
+        bgamd_env_destroy(env->rscratch);
+        env->rscratch = nullptr;
+    }
+    if (!env->rscratch) {
+        bgamd_env *sc = nullptr;
+        if ((rc = env_create(&sc, L, env->device, 0, 0, 1, 0, true))) return rc;
+        HIPCHK(hipDeviceSynchronize());                // (its reset ran on the null stream)
+        env->rscratch = sc;
+    }
+    HIPCHK(hipSetDevice(env->device));
+    bgamd_env *sc = env->rscratch;
+    scratch_borrow(env, sc);
+    if ((rc = ro_grow(P, env->r_cap_pos, {{(void **)&env->r_pos, 32}})) ||
+        (rc = ro_grow(n_fan, env->r_cap_fan, {{(void **)&env->r_fan, 32}, {(void **)&env->r_fval, 4}})) ||
+        (rc = ro_grow(N, env->r_cap_trials, {{(void **)&env->r_tval, 4}, {(void **)&env->r_tturns, 4}})) ||
+        (rc = ro_grow(L, env->r_cap_lanes, {{(void **)&env->r_lane, 4}, {(void **)&env->r_trows, 32}, {(void **)&env->r_tids, 4},
+                                            {(void **)&env->r_tv, 4}})))
+        return rc;
+    if (!env->r_ctr) HIPCHK(hipMalloc(&env->r_ctr, RO_CTRS * 8));
+    if (!env->r_host) HIPCHK(hipHostMalloc(&env->r_host, 8 * 8));
+    unsigned long long *h = env->r_host;
+
+    // the positions as rows; a bad state is refused before anything is played
+    HIPCHK(hipMemsetAsync(env->r_ctr, 0, RO_CTRS * 8, s));
+    HIPCHK(hipMemsetAsync(sc->v.counters, 0, C_COUNT * 8, s));
+    hipLaunchKernelGGL(pack_rows_kernel, grid1(P, 128), dim3(128), 0, s, d_states28, d_turn, (long long)P, env->r_pos, &env->r_ctr[RO_ERR]);
+    HIPCHK(hipMemcpyAsync(h, &env->r_ctr[RO_ERR], 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h[0] & ERRF_STATE) return BGAMD_E_STATE;
+
+    // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1
+    sc->v.seed = seed;
+    sc->v.lane_stride = 1;
+    sc->v.lane_offset = (unsigned long long)position_offset * (unsigned long long)T - (unsigned long long)L;
+    const RoView r{N, T, M, rotate ? 1 : 0, F, env->r_pos, env->r_fan, env->r_fval, env->r_lane, env->r_tval, env->r_tturns, env->r_trows,
+                   env->r_tids, env->r_ctr};
+    const int run_flags = flags & BGAMD_WEIGHTS_SLOT1;
+    const StepStreams ss{s, sc->overlap ? sc->side : s, sc->n_cu};
+    long long steps = 0;
+
+    // rotation: the first turn of every (position, ordered pair) as one greedy step with injected dice, L virtual lanes at a time
+    if (rotate) {
+        for (long long v0 = 0; v0 < n_fan; v0 += L) {
+            hipLaunchKernelGGL(ro_fan_seed_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, r);
+            GreedyRun fr;
+            if ((rc = fr.init(sc, run_flags, 0.0f, BGAMD_F32)) || (rc = fr.begin(s)) || (rc = fr.step(ss, false))) return rc;
+            hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, env->r_fan);
+            ++steps;
+        }
+        if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, nullptr, n_fan, env->r_fan, env->r_fval, nullptr, nullptr, s))) return rc;
+    }
+
+    // refill points every R turns; M > 0: R divides M - (first ply), so every trial's M-th turn ends a run
+    int R = ROLLOUT_RUN;
+    if (M > 0) {
+        const long long D = M - (rotate ? 1 : 0);
+        R = D < 1 ? 1 : (int)(D < ROLLOUT_RUN ? D : ROLLOUT_RUN);
+        while (D > 0 && D % R) --R;
+    }
+    const int G = R >= 16 ? 1 : 16 / R;                // runs between two reads of the trials-done counter (~16 turns)
+    auto refill = [&]() -> int {
+        hipLaunchKernelGGL(ro_refill_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, r);
+        if (M > 0) {                                   // truncated trials: the dense fp32 evaluator of bgamd_evaluate_slot
+            const int e = launch_eval(sc, slot, BGAMD_F32, &env->r_ctr[RO_NTRUNC], L, env->r_trows, env->r_tv, nullptr, nullptr, s);
+            if (e) return e;
+            hipLaunchKernelGGL(ro_trunc_scatter_kernel, dim3((unsigned)sc->n_cu), dim3(RO_NT), 0, s, r, (const float *)env->r_tv);
+            HIPCHK(hipMemsetAsync(&env->r_ctr[RO_NTRUNC], 0, 8, s));
+        }
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    };
+    HIPCHK(hipMemsetAsync(env->r_lane, 0xFF, (size_t)L * 4, s));
+    if ((rc = refill())) return rc;
+
+    // the loop: G runs of R turns with a refill after each, then an asynchronous read of (done, errors) into pinned memory; the host
+    // waits for the read before the last one, so the device always has a group queued
+    hipEvent_t evr[2] = {nullptr, nullptr};
+    HIPCHK(hipEventCreateWithFlags(&evr[0], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&evr[1], hipEventDisableTiming));
+    auto loop = [&]() -> int {
+        unsigned long long last_done = 0;
+        long long stalled = 0;
+        for (int k = 0;; ++k) {
+            const int b = k & 1;
+            HIPCHK(hipMemcpyAsync(h + 4 * b, &env->r_ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(h + 4 * b + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipEventRecord(evr[b], s));
+            if (k > 0) {
+                HIPCHK(hipEventSynchronize(evr[b ^ 1]));
+                const unsigned long long *hp = h + 4 * (b ^ 1);
+                if (hp[0] >= (unsigned long long)N || hp[2] || hp[3]) return BGAMD_OK;
+                stalled = hp[0] == last_done ? stalled + (long long)G * R : 0;
+                last_done = hp[0];
+                if (stalled > (long long)RO_TURN_LIMIT + 64) return BGAMD_E_INVALID;      // (cannot happen: the kernels' own limit fires first)
+            }
+            for (int gi = 0; gi < G; ++gi) {
+                GreedyRun run;
+                int e;
+                if ((e = run.init(sc, BGAMD_ROLL | run_flags, 0.0f, BGAMD_F32)) || (e = run.begin(s))) return e;
+                for (int t = 0; t < R; ++t)
+                    if ((e = run.step(ss, t + 1 < R, t == 0))) return e;
+                steps += R;
+                if ((e = refill())) return e;
+            }
+        }
+    };
+    rc = loop();
+    hipStreamSynchronize(s);
+    hipEventDestroy(evr[0]);
+    hipEventDestroy(evr[1]);
+    if (rc) return rc;
+
+    HIPCHK(hipMemcpyAsync(h, &env->r_ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + 4, &sc->v.counters[C_STEPS], 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = check_err_flags(sc, h[3]))) return rc;
+    if (h[2] & (ERRF_RO_LONG | ERRF_RO_PLY) || h[0] != (unsigned long long)N) return BGAMD_E_INVALID;
+    env->r_info[0] = L; env->r_info[1] = steps; env->r_info[2] = (int64_t)h[4]; env->r_info[3] = R;
+
+    hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)P), dim3(64), 0, s, (long long)T, (const float *)env->r_tval,
+                       (const uint32_t *)env->r_tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4])
+{
+    if (!env || !h_out) return BGAMD_E_INVALID;
+    for (int k = 0; k < 4; ++k) h_out[k] = env->r_info[k];
     return BGAMD_OK;
 }
 

@@ -55,7 +55,8 @@ enum {
                                  per lane: parity/debug use, not the throughput path)           */
     BGAMD_ONLY_P1 = 16,       /* only lanes with PLAYER1 / PLAYER2 to move take part in this call  */
     BGAMD_ONLY_P2 = 32,       /*   (head-to-head play of two policies, train.py:262-277)           */
-    BGAMD_WEIGHTS_SLOT1 = 64  /* greedy step evaluates with weight slot 1 instead of slot 0        */
+    BGAMD_WEIGHTS_SLOT1 = 64, /* greedy step evaluates with weight slot 1 instead of slot 0        */
+    BGAMD_ROLLOUT_ROTATE = 128 /* bgamd_env_rollout: trial i's first turn uses ordered dice pair i mod 36 */
 };
 
 /* value-net arithmetic.  F32: fp32-grade values (inside the 1e-5 parity bound, measured 1.8e-7).  In a greedy step the
@@ -212,6 +213,42 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream);
  * d_kept [n].  K = the last call's top_k; with top_k = 0 the largest kept count.  Any pointer may be NULL.  BGAMD_E_INVALID before
  * the first search step. */
 int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream);
+
+/* ---- Monte Carlo rollouts (TD-Gammon / GNU Backgammon rollouts, win/loss only) --------------------------------------------------------
+ * Plays T = trials games ("trials") from each of the P positions d_states28[P] / d_turn[P] (turn = side to move; d_turn NULL = PLAYER1)
+ * with the greedy policy and reports how often PLAYER1 wins.  Trial i of position p is one game:
+ *   - id and dice: j = (position_offset + p) * T + i; the dice of the trial's turn k (k = 0, 1, ...) are the TURN-stream dice of a lane with
+ *     game id j at ply k: Philox4x32-10(key = seed, counter = (j_lo, j_hi, k, STREAM_TURN)) through die_from_u32;
+ *   - BGAMD_ROLLOUT_ROTATE in flags: turn 0 uses ordered pair number i mod 36 instead, d1 = 1 + (i mod 36) / 6, d2 = 1 + (i mod 36) % 6
+ *     (T a multiple of 36: every first roll occurs exactly T / 36 times); turns k >= 1 as above;
+ *   - play: both sides as bgamd_env_step_greedy with BGAMD_ROLL (fp32 incremental value net, weight slot by BGAMD_WEIGHTS_SLOT1, the
+ *     mover's turn bit, arg-max for PLAYER1 / arg-min for PLAYER2, first index on ties, no special case for terminal afterstates); a pass
+ *     is a turn;
+ *   - outcome: a game that ends scores 1.0 if PLAYER1 won, else 0.0; a position that is already over scores its winner at 0 turns;
+ *   - max_plies = M > 0: a trial still running after its M-th turn stops there and scores the fp32 net's value (same slot) of the board
+ *     reached with the turn bit of the side now to move -- bit-identical to bgamd_evaluate_slot(..., BGAMD_F32) of that state and turn.
+ *     M = 0 plays every trial to its end (BGAMD_E_INVALID if a trial is still running after 100 000 turns).
+ * Per position (any pointer may be NULL): d_mean[P] = (1/T) sum x_i;  d_stderr[P] = sqrt(sum (x_i - mean)^2 / (T (T - 1))), 0 for T = 1 --
+ * with rotation this is the plain, conservative estimate (the stratification by first roll is not credited);  d_turns[P] (int64) = total
+ * turns played;  d_truncated[P] = trials scored by the net.  Per trial (optional): d_trial_value[P][T], d_trial_turns[P][T].
+ * Results depend only on (positions, position_offset, T, M, flags, seed, weights): bit for bit the same for any `lanes` (the internal lane
+ * count, 0 = default: min(65 536, P T rounded up to 256)) and from call to call; the statistics are reduced in a fixed order.  Splitting the
+ * positions over calls (or ranks) with position_offset gives the same trials.
+ * No side effect on this env: its lanes, dice, ply / episode, counters, last_choice and search results are untouched.  The trials run on
+ * an internal scratch env of `lanes` lanes (created on first use, re-created when the lane count changes, freed by bgamd_env_destroy;
+ * ~1.7 GB at 65 536 lanes) that uses this env's weight tables; buffers of O(P T) bytes are kept between calls.
+ * Errors: P < 1, T < 1, M < 0, lanes < 0, position_offset < 0, P T >= 2^31 or flags other than BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1:
+ * BGAMD_E_INVALID; a bad state: BGAMD_E_STATE; an empty weight slot: BGAMD_E_NOWEIGHTS; arena overflow and delta errors of the greedy
+ * kernels: BGAMD_E_ARENA / BGAMD_E_DELTA.
+ * SYNCHRONISES the stream before it returns (it must know when the last trial has ended; the host reads a trials-done counter about every
+ * 16 turns). */
+int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n_positions,
+                      int64_t position_offset, int64_t trials, int64_t max_plies, uint64_t seed, int64_t lanes,
+                      double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
+                      float *d_trial_value, int32_t *d_trial_turns, void *stream);
+/* Diagnostics of the last rollout (host values): h_out = [lanes, env steps issued (rotation steps included), lane-steps that played a
+ * turn of a live trial, turns per run between refill points].  Idle share = 1 - h_out[2] / (h_out[0] h_out[1]). */
+int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4]);
 
 /* (slot 8 below counts the 32-row x 2-feature MFMA steps of the dense f32 net, or the W1 columns added by the
  * incremental one) */

@@ -1,0 +1,89 @@
+"""Throughput of the Monte Carlo rollout (bgamd_env_rollout) at 65 536 lanes: full rollouts (64 mid-game positions x 16 384 rotated
+trials, played to the end) and truncated ones (the same positions at M = 7 and M = 0, as a pair), set against the greedy step's env
+steps/s measured in the same run.  One JSON line per configuration: ms per call (median of --regions timed calls after a warm-up call),
+trials/s, trial-turns/s (turns of all trials / time), their ratio to the greedy step, and the idle share (lane-steps on lanes without a
+live trial / all lane-steps, from bgamd_env_rollout_info)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "backgammon-engine_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _greedy_ms(env, steps, regions):
+    env.run_greedy(steps)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(regions):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        env.run_greedy(steps)
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b) / steps)
+    return statistics.median(ms)
+
+
+def _positions(bg, w, n, seed):
+    """n mid-game positions: greedy play from the start position, lane k stopped after 10 + k turns."""
+    e = bg.VecGame(max(n, 64), seed=seed)
+    e.load_weights(w)
+    e.run_greedy(10)
+    st, tu = [], []
+    for k in range(n):
+        e.step_greedy()
+        st.append(e.states()[k].cpu().numpy()); tu.append(int(e.turns()[k]))
+    e.close()
+    return np.array(st, np.int32), np.array(tu, np.int32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lanes", type=int, default=65536)
+    ap.add_argument("--positions", type=int, default=64)
+    ap.add_argument("--trials", type=int, default=16384)
+    ap.add_argument("--regions", type=int, default=3)
+    a = ap.parse_args()
+    import backgammon_env as bg
+    w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
+    st, tu = _positions(bg, w, a.positions, 1)
+    env = bg.VecGame(a.lanes, seed=1)
+    env.load_weights(w)
+    g_ms = _greedy_ms(env, 20, 5)
+    greedy_sps = a.lanes / g_ms * 1e3
+    out = []
+    for name, M in (("full", 0), ("truncated", 7), ("truncated", 0)):
+        env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes)       # warm-up (scratch env, buffers)
+        ms = []
+        for _ in range(a.regions):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes)
+            ms.append((time.perf_counter() - t0) * 1e3)            # (the call synchronises)
+        info = env.rollout_info()
+        m = statistics.median(ms)
+        n_trials = a.positions * a.trials
+        turns = int(r["turns"].sum())
+        idle = 1.0 - info[2] / float(info[0] * info[1])
+        rec = {"config": name, "max_plies": M, "lanes": info[0], "positions": a.positions, "trials": a.trials, "ms": round(m, 2),
+               "trials_per_s": round(n_trials / m * 1e3), "trial_turns_per_s": round(turns / m * 1e3),
+               "greedy_env_steps_per_s": round(greedy_sps), "ratio_to_greedy": round(turns / m * 1e3 / greedy_sps, 3),
+               "idle_share": round(idle, 4), "env_steps": info[1], "turns_per_run": info[3], "mean_turns": round(turns / n_trials, 2),
+               "truncated": int(r["truncated"].sum()), "regions_ms": [round(x, 2) for x in ms]}
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    env.close()
+    print(json.dumps({"rollout_bench": out}))
+
+
+if __name__ == "__main__":
+    main()
