@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import (AUTO_RESET, BF16, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1, ONLY_P2, ROLL, ROLLOUT_ROTATE, WANT_INDEX,  # noqa: F401
-                    WEIGHTS_SLOT1, BgamdError)
+from ._capi import (AUTO_RESET, BF16, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1, ONLY_P2, ROLL, ROLLOUT_ROTATE, ROLLOUT_VR,  # noqa: F401
+                    WANT_INDEX, WEIGHTS_SLOT1, BgamdError)
 
 __all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "BgamdError", "set_seed", "pack_rows"]
 
@@ -36,6 +36,9 @@ ERR_MESSAGES = {                                   # cppsrc/game.cpp:585-642, in
     4: "Cannot move in that direction.", 5: "Move does not match dice.", 6: "Invalid destination.",
     7: "Cannot bear off from jail",
 }
+
+# the 21 unordered rolls in the order of VecGame.evaluate_preroll's columns (and of the search): (1,1), (1,2), ..., (1,6), (2,2), ..., (6,6)
+ROLLS = [(a, b) for a in range(1, 7) for b in range(a, 7)]
 
 _seed = int.from_bytes(os.urandom(8), "little")    # reference: random_device (game.hpp:45)
 _next_scalar_id = 0
@@ -281,13 +284,28 @@ class VecGame:
             _capi.check(self._lib.bgamd_env_search_read(self._h, _ptr(st), _ptr(v1), _ptr(v2), None, _stream()), "search_read")
         return st, v1, v2, kept
 
+    def evaluate_preroll(self, states28, turn, slot=0):
+        """1-ply pre-roll evaluation (include/bgamd.h, bgamd_env_evaluate_preroll): for each position with `turn` to roll, the value of the
+        greedy step's choice for each of the 21 rolls in ROLLS' order (the net's value of the position when the roll has no move; the
+        outcome for a position that is over) and their probability-weighted mean.  -> (roll_values [n, 21] float32, mean [n] float64)"""
+        st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
+        n = st.shape[0]
+        t = self._dev(turn, torch.int32, (n,))
+        f, m = self._buf((n, 21), torch.float32), self._buf((n,), torch.float64)
+        _capi.check(self._lib.bgamd_env_evaluate_preroll(self._h, WEIGHTS_SLOT1 if slot else 0, _ptr(st), _ptr(t), n, _ptr(f), _ptr(m),
+                                                         _stream()), "evaluate_preroll")
+        return f, m
+
     def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
-                per_trial=False):
+                per_trial=False, variance_reduction=False):
         """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
         move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
         trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
         env's weights (slot) are used; its own lanes are untouched.  -> dict of device tensors: mean [P] (float64, the share of PLAYER1
-        wins), stderr [P], turns [P] (int64), truncated [P] (int32); per_trial: also trial_value [P, T] (float32), trial_turns [P, T]."""
+        wins), stderr [P], turns [P] (int64), truncated [P] (int32); per_trial: also trial_value [P, T] (float32), trial_turns [P, T].
+        variance_reduction: also the luck-adjusted vr_mean [P] and vr_stderr [P] (float64; BGAMD_ROLLOUT_VR: every turn's luck against
+        the pre-roll evaluation is subtracted from the trial's value), with per_trial trial_luck [P, T] (float64); the plain outputs are
+        the same as without it."""
         st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
         P, T = st.shape[0], int(trials)
         t = self._dev(turn, torch.int32, (P,))
@@ -296,11 +314,17 @@ class VecGame:
         if per_trial:
             out["trial_value"] = self._buf((P, max(T, 0)), torch.float32)
             out["trial_turns"] = self._buf((P, max(T, 0)), torch.int32)
-        flags = (ROLLOUT_ROTATE if rotate else 0) | (WEIGHTS_SLOT1 if slot else 0)
+        flags = (ROLLOUT_ROTATE if rotate else 0) | (WEIGHTS_SLOT1 if slot else 0) | (ROLLOUT_VR if variance_reduction else 0)
         _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
                                                 int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
                                                 _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
                                                 _ptr(out.get("trial_turns")), _stream()), "rollout")
+        if variance_reduction:
+            out["vr_mean"], out["vr_stderr"] = self._buf((P,), torch.float64), self._buf((P,), torch.float64)
+            if per_trial:
+                out["trial_luck"] = self._buf((P, T), torch.float64)
+            _capi.check(self._lib.bgamd_env_rollout_vr_read(self._h, _ptr(out["vr_mean"]), _ptr(out["vr_stderr"]),
+                                                            _ptr(out.get("trial_luck")), _stream()), "rollout_vr_read")
         return out
 
     def rollout_info(self):

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("BGAMD_LIB") or os.path.join(os.path.dirname(_HERE), "
 OK = 0
 ROLL, AUTO_RESET, NO_FLIP, WANT_INDEX, ONLY_P1, ONLY_P2, WEIGHTS_SLOT1 = 1, 2, 4, 8, 16, 32, 64
 ROLLOUT_ROTATE = 128
+ROLLOUT_VR = 256
 F32, BF16, F16X2, F32_DENSE = 0, 1, 2, 3
 
 # every symbol include/bgamd.h declares: (name, restype, argtypes)
@@ -63,6 +64,8 @@ SYMBOLS = [
     ("bgamd_env_rollout", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
                                     _P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_rollout_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("bgamd_env_evaluate_preroll", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, _P]),
+    ("bgamd_env_rollout_vr_read", C.c_int, [_P, _P, _P, _P, _P]),
     ("bgamd_env_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("bgamd_env_reset_stats", C.c_int, [_P, _P]),
     ("bgamd_env_try_move", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),

@@ -636,6 +636,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 #include "bg_random_kernels.h"
 #include "bg_search.h"
 #include "bg_rollout.h"
+#include "bg_vr.h"
 
 }  // namespace
 
@@ -740,6 +741,15 @@ struct bgamd_env {
     unsigned long long *r_ctr = nullptr, *r_host = nullptr;        // r_host: pinned, [2][2] (done, error bits) of the last two reads
     long long r_cap_pos = 0, r_cap_fan = 0, r_cap_trials = 0, r_cap_lanes = 0;
     int64_t r_info[4] = {0, 0, 0, 0};      // bgamd_env_rollout_info
+    // pre-roll evaluation and luck-adjusted rollouts (bg_vr.h): both score their (position, roll) roots on the search's scratch env
+    uint4 *p_rows = nullptr;
+    float *p_f = nullptr;
+    unsigned long long *p_ctr = nullptr;
+    long long p_cap = 0;
+    double *r_tluck = nullptr, *r_m0 = nullptr;                     // r_tluck [P T] luck totals, r_m0 [P] / r_f0 [P][21]: turn 0 (rotation)
+    float *r_vf = nullptr, *r_f0 = nullptr;                         // r_vf [L][21]: the trial lanes' f of the turn at hand
+    long long r_cap_vtrials = 0, r_cap_vlanes = 0, r_cap_vpos = 0;
+    long long r_vr_P = 0, r_vr_T = 0;      // P, T of the last rollout if it had BGAMD_ROLLOUT_VR (0: bgamd_env_rollout_vr_read refuses)
 };
 
 namespace {
@@ -1015,7 +1025,8 @@ int bgamd_env_destroy(bgamd_env *env)
     {
         void *sp[] = {env->s_cnt, env->s_off, env->s_fill, env->s_kept, env->s_koff, env->s_max, env->s_grp, env->s_rank, env->c_rows,
                       env->c_key, env->c_v1, env->c_v2, env->c_rval, env->r_pos, env->r_fan, env->r_trows, env->r_fval, env->r_tval,
-                      env->r_tv, env->r_tturns, env->r_lane, env->r_tids, env->r_ctr};
+                      env->r_tv, env->r_tturns, env->r_lane, env->r_tids, env->r_ctr, env->p_rows, env->p_f, env->p_ctr,
+                      env->r_tluck, env->r_m0, env->r_vf, env->r_f0};
         for (void *p : sp) if (p) hipFree(p);
         if (env->r_host) hipHostFree(env->r_host);
     }
@@ -1716,6 +1727,26 @@ static void scratch_borrow(const bgamd_env *env, bgamd_env *sc)
     sc->d_lut = env->d_lut; sc->d_lut16 = env->d_lut16;
 }
 
+// the search's scratch env, with at least min(SEARCH_CHUNK, n_virtual rounded up to 256) lanes (re-created when it has fewer)
+static int search_scratch(bgamd_env *env, long long n_virtual, hipStream_t s)
+{
+    const long long want = n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK;
+    if (env->scratch && env->scratch->v.n < want) {
+        HIPCHK(hipStreamSynchronize(s));
+        bgamd_env_destroy(env->scratch);
+        env->scratch = nullptr;
+    }
+    if (!env->scratch) {
+        bgamd_env *sc = nullptr;
+        const int rc = env_create(&sc, want, env->device, 0, 0, 0, 0, true);
+        if (rc) return rc;
+        HIPCHK(hipDeviceSynchronize());                // (its reset ran on the null stream)
+        env->scratch = sc;
+    }
+    HIPCHK(hipSetDevice(env->device));
+    return BGAMD_OK;
+}
+
 static int search_grow(bgamd_env *env, long long need)
 {
     if (need <= env->c_cap) return BGAMD_OK;
@@ -1791,19 +1822,7 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
     const int slot = run.slot;
     const long long n_virtual = n_cand * SRCH_ROLLS;
     if (n_virtual > 0) {
-        long long want = n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK;
-        if (env->scratch && env->scratch->v.n < want) {
-            HIPCHK(hipStreamSynchronize(s));
-            bgamd_env_destroy(env->scratch);
-            env->scratch = nullptr;
-        }
-        if (!env->scratch) {
-            bgamd_env *sc = nullptr;
-            if ((rc = env_create(&sc, want, env->device, 0, 0, 0, 0, true))) return rc;
-            HIPCHK(hipDeviceSynchronize());            // (its reset ran on the null stream)
-            env->scratch = sc;
-        }
-        HIPCHK(hipSetDevice(env->device));
+        if ((rc = search_scratch(env, n_virtual, s))) return rc;
         bgamd_env *sc = env->scratch;
         scratch_borrow(env, sc);                       // the tables of this env as they are now: a reload is seen
         const float *w2 = env->d_w[slot] + N_HID * N_IN + N_HID, *b2 = w2 + N_HID;
@@ -1865,13 +1884,80 @@ static int ro_grow(long long need, long long &cap, std::initializer_list<std::pa
     return BGAMD_OK;
 }
 
+// ---- pre-roll evaluation (bg_vr.h) ---------------------------------------------------------------------------------------
+// f of n positions x 21 rolls: the positions are rows[n] (src NULL) or the lanes of the env src (n = its lane count); every (position,
+// roll) is a virtual lane of the search's scratch env (search_scratch: ready, weights borrowed), scored as the search's stage C scores
+// its roots.  Writes f[q][r] of every position that is neither over nor a finished lane.
+static int preroll_pass(bgamd_env *env, int slot, long long n, const uint4 *rows, const EnvView *src, float *f, hipStream_t s)
+{
+    bgamd_env *sc = env->scratch;
+    const float *w2 = env->d_w[slot] + N_HID * N_IN + N_HID, *b2 = w2 + N_HID;
+    const StepStreams sss{s, s, sc->n_cu};
+    const long long n_virtual = n * SRCH_ROLLS;
+    for (long long v0 = 0; v0 < n_virtual; v0 += sc->v.n) {
+        if (src)
+            hipLaunchKernelGGL(pre_fanout_kernel<true>, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, v0, n, (const uint4 *)nullptr, *src);
+        else
+            hipLaunchKernelGGL(pre_fanout_kernel<false>, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, v0, n, rows, sc->v);
+        GreedyRun sr;
+        int rc;
+        if ((rc = sr.init(sc, slot ? BGAMD_WEIGHTS_SLOT1 : 0, 0.0f, BGAMD_F32)) || (rc = sr.begin(s)) || (rc = sr.step(sss, false, true, true)))
+            return rc;
+        hipLaunchKernelGGL(srch_collect_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, (const unsigned long long *)sc->sv.best,
+                           (const float *)sc->sv.root_hidden, w2, b2, v0, f);
+    }
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+// the error bits the scratch env's greedy kernels raised since it was cleared -> host (synchronises), cleared again
+static int preroll_errors(bgamd_env *env, hipStream_t s)
+{
+    unsigned long long h = 0;
+    HIPCHK(hipMemcpyAsync(&h, &env->scratch->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return check_err_flags(env->scratch, h);
+}
+
+int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n,
+                               float *d_roll_values, double *d_mean, void *stream)
+{
+    if (!env || !d_states28 || n < 1 || n >= (1ll << 31) / SRCH_ROLLS || (flags & ~BGAMD_WEIGHTS_SLOT1)) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    const int slot = (flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
+    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = ro_grow(n, env->p_cap, {{(void **)&env->p_rows, 32}, {(void **)&env->p_f, 4 * SRCH_ROLLS}}))) return rc;
+    if (!env->p_ctr) HIPCHK(hipMalloc(&env->p_ctr, 8));
+
+    // the positions as rows; a bad state is refused before anything is scored
+    unsigned long long h = 0;
+    HIPCHK(hipMemsetAsync(env->p_ctr, 0, 8, s));
+    hipLaunchKernelGGL(pack_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_turn, (long long)n, env->p_rows, env->p_ctr);
+    HIPCHK(hipMemcpyAsync(&h, env->p_ctr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h & ERRF_STATE) return BGAMD_E_STATE;
+
+    if ((rc = search_scratch(env, n * SRCH_ROLLS, s))) return rc;
+    scratch_borrow(env, env->scratch);
+    HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
+    if ((rc = preroll_pass(env, slot, n, env->p_rows, nullptr, env->p_f, s))) return rc;
+    hipLaunchKernelGGL(pre_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)n, (const uint4 *)env->p_rows, env->p_f,
+                       d_roll_values, d_mean);
+    HIPCHK(hipGetLastError());
+    return preroll_errors(env, s);
+}
+
 int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n_positions,
                       int64_t position_offset, int64_t trials, int64_t max_plies, uint64_t seed, int64_t lanes,
                       double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
                       float *d_trial_value, int32_t *d_trial_turns, void *stream)
 {
+    if (env) env->r_vr_P = 0;                          // (bgamd_env_rollout_vr_read: only after a call that had the flag)
     if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
-    if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1)) return BGAMD_E_INVALID;
+    if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1 | BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
     if (n_positions >= (1ll << 31) || trials >= (1ll << 31) || n_positions * trials >= (1ll << 31) || lanes > (1ll << 30))
         return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
@@ -1879,7 +1965,7 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
     hipStream_t s = (hipStream_t)stream;
     const long long P = n_positions, T = trials, N = P * T, M = max_plies;
-    const bool rotate = (flags & BGAMD_ROLLOUT_ROTATE) != 0;
+    const bool rotate = (flags & BGAMD_ROLLOUT_ROTATE) != 0, vr = (flags & BGAMD_ROLLOUT_VR) != 0;
     const long long F = rotate ? (T < 36 ? T : 36) : 0, n_fan = P * F;
     const long long L = lanes > 0 ? lanes : (N < ROLLOUT_LANES ? ((N + 255) / 256) * 256 : ROLLOUT_LANES);
     int rc;
@@ -1904,6 +1990,10 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
         (rc = ro_grow(N, env->r_cap_trials, {{(void **)&env->r_tval, 4}, {(void **)&env->r_tturns, 4}})) ||
         (rc = ro_grow(L, env->r_cap_lanes, {{(void **)&env->r_lane, 4}, {(void **)&env->r_trows, 32}, {(void **)&env->r_tids, 4},
                                             {(void **)&env->r_tv, 4}})))
+        return rc;
+    if (vr && ((rc = ro_grow(N, env->r_cap_vtrials, {{(void **)&env->r_tluck, 8}})) ||
+               (rc = ro_grow(L, env->r_cap_vlanes, {{(void **)&env->r_vf, 4 * SRCH_ROLLS}})) ||
+               (rc = ro_grow(P, env->r_cap_vpos, {{(void **)&env->r_f0, 4 * SRCH_ROLLS}, {(void **)&env->r_m0, 8}}))))
         return rc;
     if (!env->r_ctr) HIPCHK(hipMalloc(&env->r_ctr, RO_CTRS * 8));
     if (!env->r_host) HIPCHK(hipHostMalloc(&env->r_host, 8 * 8));
@@ -1938,6 +2028,31 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
         }
         if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, nullptr, n_fan, env->r_fan, env->r_fval, nullptr, nullptr, s))) return rc;
     }
+
+    // luck adjustment: the pre-roll evaluation on the search's scratch env -- of the P positions once (rotation: turn 0's luck), then
+    // of the trial lanes before every turn (vr_turn); every trial's luck total starts at 0 or at its turn-0 luck
+    if (vr) {
+        const long long pv = (rotate ? P : 0) > L ? P : L;
+        if ((rc = search_scratch(env, pv * SRCH_ROLLS, s))) return rc;
+        scratch_borrow(env, env->scratch);
+        HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
+        if (rotate) {
+            if ((rc = preroll_pass(env, slot, P, env->r_pos, nullptr, env->r_f0, s))) return rc;
+            hipLaunchKernelGGL(pre_reduce_kernel, grid1(P, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)P, (const uint4 *)env->r_pos, env->r_f0,
+                               (float *)nullptr, env->r_m0);
+        }
+        hipLaunchKernelGGL(ro_vr_init_kernel, dim3((unsigned)(sc->n_cu * 4)), dim3(RO_NT), 0, s, r, (const float *)env->r_f0,
+                           (const double *)env->r_m0, env->r_tluck);
+        HIPCHK(hipGetLastError());
+    }
+    // (the roots of the turn at hand are in place: the board, side to move and dice of every live trial lane)
+    auto vr_turn = [&]() -> int {
+        const int e = preroll_pass(env, slot, L, nullptr, &sc->v, env->r_vf, s);
+        if (e) return e;
+        hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)env->r_lane, (const float *)env->r_vf,
+                           env->r_tluck);
+        return BGAMD_OK;
+    };
 
     // refill points every R turns; M > 0: R divides M - (first ply), so every trial's M-th turn ends a run
     int R = ROLLOUT_RUN;
@@ -1987,7 +2102,7 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
                 int e;
                 if ((e = run.init(sc, BGAMD_ROLL | run_flags, 0.0f, BGAMD_F32)) || (e = run.begin(s))) return e;
                 for (int t = 0; t < R; ++t)
-                    if ((e = run.step(ss, t + 1 < R, t == 0))) return e;
+                    if ((vr && (e = vr_turn())) || (e = run.step(ss, t + 1 < R, t == 0))) return e;
                 steps += R;
                 if ((e = refill())) return e;
             }
@@ -2005,12 +2120,14 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     HIPCHK(hipStreamSynchronize(s));
     if ((rc = check_err_flags(sc, h[3]))) return rc;
     if (h[2] & (ERRF_RO_LONG | ERRF_RO_PLY) || h[0] != (unsigned long long)N) return BGAMD_E_INVALID;
+    if (vr && (rc = preroll_errors(env, s))) return rc;
     env->r_info[0] = L; env->r_info[1] = steps; env->r_info[2] = (int64_t)h[4]; env->r_info[3] = R;
 
     hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)P), dim3(64), 0, s, (long long)T, (const float *)env->r_tval,
                        (const uint32_t *)env->r_tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
+    if (vr) { env->r_vr_P = P; env->r_vr_T = T; }
     return BGAMD_OK;
 }
 
@@ -2018,6 +2135,16 @@ int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4])
 {
     if (!env || !h_out) return BGAMD_E_INVALID;
     for (int k = 0; k < 4; ++k) h_out[k] = env->r_info[k];
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_vr_read(bgamd_env *env, double *d_vr_mean, double *d_vr_stderr, double *d_trial_luck, void *stream)
+{
+    ENV_GUARD(env);
+    if (env->r_vr_P < 1) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL(ro_vr_reduce_kernel, dim3((unsigned)env->r_vr_P), dim3(64), 0, (hipStream_t)stream, (long long)env->r_vr_T,
+                       (const float *)env->r_tval, (const double *)env->r_tluck, d_vr_mean, d_vr_stderr, d_trial_luck);
+    HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
 

@@ -56,7 +56,8 @@ enum {
     BGAMD_ONLY_P1 = 16,       /* only lanes with PLAYER1 / PLAYER2 to move take part in this call  */
     BGAMD_ONLY_P2 = 32,       /*   (head-to-head play of two policies, train.py:262-277)           */
     BGAMD_WEIGHTS_SLOT1 = 64, /* greedy step evaluates with weight slot 1 instead of slot 0        */
-    BGAMD_ROLLOUT_ROTATE = 128 /* bgamd_env_rollout: trial i's first turn uses ordered dice pair i mod 36 */
+    BGAMD_ROLLOUT_ROTATE = 128, /* bgamd_env_rollout: trial i's first turn uses ordered dice pair i mod 36 */
+    BGAMD_ROLLOUT_VR = 256    /* bgamd_env_rollout: also compute luck-adjusted results, read with bgamd_env_rollout_vr_read */
 };
 
 /* value-net arithmetic.  F32: fp32-grade values (inside the 1e-5 parity bound, measured 1.8e-7).  In a greedy step the
@@ -237,8 +238,8 @@ int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, floa
  * No side effect on this env: its lanes, dice, ply / episode, counters, last_choice and search results are untouched.  The trials run on
  * an internal scratch env of `lanes` lanes (created on first use, re-created when the lane count changes, freed by bgamd_env_destroy;
  * ~1.7 GB at 65 536 lanes) that uses this env's weight tables; buffers of O(P T) bytes are kept between calls.
- * Errors: P < 1, T < 1, M < 0, lanes < 0, position_offset < 0, P T >= 2^31 or flags other than BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1:
- * BGAMD_E_INVALID; a bad state: BGAMD_E_STATE; an empty weight slot: BGAMD_E_NOWEIGHTS; arena overflow and delta errors of the greedy
+ * Errors: P < 1, T < 1, M < 0, lanes < 0, position_offset < 0, P T >= 2^31 or flags other than BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1 |
+ * BGAMD_ROLLOUT_VR (below): BGAMD_E_INVALID; a bad state: BGAMD_E_STATE; an empty weight slot: BGAMD_E_NOWEIGHTS; arena overflow and delta errors of the greedy
  * kernels: BGAMD_E_ARENA / BGAMD_E_DELTA.
  * SYNCHRONISES the stream before it returns (it must know when the last trial has ended; the host reads a trials-done counter about every
  * 16 turns). */
@@ -249,6 +250,50 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
 /* Diagnostics of the last rollout (host values): h_out = [lanes, env steps issued (rotation steps included), lane-steps that played a
  * turn of a live trial, turns per run between refill points].  Idle share = 1 - h_out[2] / (h_out[0] h_out[1]). */
 int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4]);
+
+/* ---- 1-ply pre-roll evaluation (GNU Backgammon's "evaluation before the roll") ------------------------------------------------------
+ * For each of the n positions s = d_states28[n] with the side to roll m = d_turn[n] (NULL = PLAYER1), what the roller can expect from
+ * each of the 21 unordered rolls r = (1,1), (1,2), ..., (1,6), (2,2), ..., (6,6), in that order (the search's roll order):
+ *   - f(s, r) is exactly the R(c, r) of the search's item 4 with s in the place of c and the roller in the opponent's role: when the
+ *     roller has a move, the value of the afterstate the greedy step would choose (F32 incremental value net, the roller's turn bit,
+ *     arg-max for PLAYER1 / arg-min for PLAYER2, no special case for terminal afterstates); when the roller has no move, the net's value
+ *     of s with the roller's turn bit; a position that is already over (15 off for either side) gives its outcome, 1.0 if PLAYER1 has
+ *     won, else 0.0, for every roll;
+ *   - mean(s) = sum over the 21 rolls in order of w_r * (double) f(s, r) in fp64, w_r = 1.0/36.0 for a double and 2.0/36.0 otherwise
+ *     (a rounded product and a rounded sum per roll, no fused multiply-add).
+ * Out (either may be NULL): d_roll_values[n][21] (fp32), d_mean[n] (fp64).  flags: 0 or BGAMD_WEIGHTS_SLOT1 (the weight slot).  A
+ * position's values depend on nothing else in the call (not on the other positions, n or the chunking).
+ * No side effect on this env: its lanes, dice, ply / episode, counters, last_choice, search results and rollout results are untouched.
+ * The n x 21 (position, roll) pairs are scored by the greedy step's own kernels on the search's internal scratch env.
+ * Errors: n < 1 or other flags: BGAMD_E_INVALID; a bad state: BGAMD_E_STATE; an empty weight slot: BGAMD_E_NOWEIGHTS; arena overflow and
+ * delta errors of the greedy kernels: BGAMD_E_ARENA / BGAMD_E_DELTA.  SYNCHRONISES the stream (a bad state is refused before anything is
+ * scored; the scratch env's error bits are read at the end). */
+int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n,
+                               float *d_roll_values, double *d_mean, void *stream);
+
+/* ---- luck-adjusted rollouts (BGAMD_ROLLOUT_VR; GNU Backgammon's variance reduction) ------------------------------------------------
+ * With BGAMD_ROLLOUT_VR in its flags, bgamd_env_rollout also charges every trial with the luck of its rolls:
+ *   - the played trials are unchanged: every output of the call (mean, stderr, turns, truncated, per-trial value and turns) and
+ *     bgamd_env_rollout_info are bit-identical to the same call without the flag;
+ *   - luck of a turn: trial i plays turns k = 0 ... K_i - 1; before turn k its board is s_k with m_k to roll, the turn is played with
+ *     dice (a, b) and r_k is their unordered roll.  luck_k = (double) f(s_k, r_k) - mean(s_k), with f and mean bit-identical to what
+ *     bgamd_env_evaluate_preroll returns for (s_k, m_k) with the rollout's weight slot.  A pass is a turn with a luck like any other;
+ *     the last turn of a game counts too;
+ *   - rotation: turn 0 of trial i is played with ordered pair i mod 36, and its luck uses the pre-roll evaluation of the position
+ *     itself (evaluated once per call).  Over a multiple of 36 trials the turn-0 lucks cancel (up to rounding): the adjusted stderr
+ *     credits the stratification by first roll that the plain one does not;
+ *   - truncation (max_plies = M > 0): turns 0 ... M - 1 count; the trial's value x_i is the plain one.  A position that is already over
+ *     has L = 0;
+ *   - per trial: L_i = sum of luck_k in fp64, in turn order, from 0.0; the adjusted value is y_i = (double) x_i - L_i;
+ *   - per position: vr_mean = (1/T) sum y_i;  vr_stderr = sqrt(sum (y_i - vr_mean)^2 / (T (T - 1))), 0 for T = 1; both reduced in the
+ *     fixed order of the plain statistics.  Like them, bit for bit the same for any `lanes`, from call to call and over position_offset
+ *     splits.
+ * Why it is unbiased: E[luck_k | history] = 0 because r_k is drawn from the same 1/36 and 2/36 distribution the mean uses
+ * (die_from_u32 is uniform to within 2^-32 per die), so E[y_i] = E[x_i].
+ * Cost: before every turn of every trial the 21 rolls of its position are scored (21 virtual roots on the search's scratch env). */
+/* The luck-adjusted results of the last bgamd_env_rollout, which must have had BGAMD_ROLLOUT_VR (else BGAMD_E_INVALID): d_vr_mean[P],
+ * d_vr_stderr[P], d_trial_luck[P][T] = L_i (fp64, any may be NULL; P and T of that call).  Stream-ordered. */
+int bgamd_env_rollout_vr_read(bgamd_env *env, double *d_vr_mean, double *d_vr_stderr, double *d_trial_luck, void *stream);
 
 /* (slot 8 below counts the 32-row x 2-feature MFMA steps of the dense f32 net, or the W1 columns added by the
  * incremental one) */

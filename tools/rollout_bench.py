@@ -2,7 +2,12 @@
 trials, played to the end) and truncated ones (the same positions at M = 7 and M = 0, as a pair), set against the greedy step's env
 steps/s measured in the same run.  One JSON line per configuration: ms per call (median of --regions timed calls after a warm-up call),
 trials/s, trial-turns/s (turns of all trials / time), their ratio to the greedy step, and the idle share (lane-steps on lanes without a
-live trial / all lane-steps, from bgamd_env_rollout_info)."""
+live trial / all lane-steps, from bgamd_env_rollout_info).
+
+--vr: luck-adjusted rollouts (BGAMD_ROLLOUT_VR) instead, full (M = 0) and truncated (M = 7), --vr-trials rotated trials per position.  For
+each: the plain call and the VR call of the same trials, ms per call, the VR pass's virtual roots/s (21 per trial-turn over the time the
+VR call adds), the per-position variance ratio (stderr / vr_stderr)^2 (median, min, max, pooled) and effective trials/s (trials/s x the
+median ratio; 1 for the plain call)."""
 import argparse
 import json
 import os
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--positions", type=int, default=64)
     ap.add_argument("--trials", type=int, default=16384)
     ap.add_argument("--regions", type=int, default=3)
+    ap.add_argument("--vr", action="store_true", help="luck-adjusted rollouts against plain ones")
+    ap.add_argument("--vr-trials", type=int, default=2592)
     a = ap.parse_args()
     import backgammon_env as bg
     w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
@@ -60,6 +67,10 @@ def main():
     env.load_weights(w)
     g_ms = _greedy_ms(env, 20, 5)
     greedy_sps = a.lanes / g_ms * 1e3
+    if a.vr:
+        _vr(env, st, tu, a, greedy_sps)
+        env.close()
+        return
     out = []
     for name, M in (("full", 0), ("truncated", 7), ("truncated", 0)):
         env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes)       # warm-up (scratch env, buffers)
@@ -83,6 +94,46 @@ def main():
         out.append(rec)
     env.close()
     print(json.dumps({"rollout_bench": out}))
+
+
+def _timed(env, st, tu, trials, M, lanes, regions, vr):
+    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr)      # warm-up
+    ms = []
+    for _ in range(regions):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr)
+        ms.append((time.perf_counter() - t0) * 1e3)                # (the call synchronises; vr_read is stream-ordered after it)
+    torch.cuda.synchronize()
+    return statistics.median(ms), r, ms
+
+
+def _vr(env, st, tu, a, greedy_sps):
+    out = []
+    for name, M in (("full", 0), ("truncated", 7)):
+        ms_p, rp, _ = _timed(env, st, tu, a.vr_trials, M, a.lanes, a.regions, False)
+        ms_v, rv, regions = _timed(env, st, tu, a.vr_trials, M, a.lanes, a.regions, True)
+        info = env.rollout_info()
+        se, vse = rv["stderr"].cpu().numpy(), rv["vr_stderr"].cpu().numpy()
+        live = (se > 0) & (vse > 0)
+        ratio = se[live] ** 2 / vse[live] ** 2
+        med = float(np.median(ratio))
+        n_trials = a.positions * a.vr_trials
+        turns = int(rp["turns"].sum())
+        roots = 21 * turns
+        rec = {"config": name, "max_plies": M, "lanes": info[0], "positions": a.positions, "trials": a.vr_trials,
+               "plain_ms": round(ms_p, 2), "vr_ms": round(ms_v, 2), "cost_ratio": round(ms_v / ms_p, 2),
+               "vr_virtual_roots_per_s": round(roots / (ms_v - ms_p) * 1e3),
+               "greedy_env_steps_per_s": round(greedy_sps), "vr_roots_to_greedy": round(roots / (ms_v - ms_p) * 1e3 / greedy_sps, 3),
+               "variance_ratio_median": round(med, 3), "variance_ratio_min": round(float(ratio.min()), 3),
+               "variance_ratio_max": round(float(ratio.max()), 3), "variance_ratio_pooled": round(float((se[live] ** 2).sum() /
+                                                                                                     (vse[live] ** 2).sum()), 3),
+               "plain_effective_trials_per_s": round(n_trials / ms_p * 1e3),
+               "vr_effective_trials_per_s": round(n_trials / ms_v * 1e3 * med),
+               "mean_turns": round(turns / n_trials, 2), "vr_regions_ms": [round(x, 2) for x in regions]}
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    print(json.dumps({"rollout_vr_bench": out}))
 
 
 if __name__ == "__main__":
