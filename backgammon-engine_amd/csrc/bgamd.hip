@@ -9,6 +9,7 @@
 // Greedy step: roots -> stage<PLY2> -> stage<PLY3> -> stage<LEAF> (bg_staged_kernels.h) -> eval (bg_eval.h) -> apply.
 // Random step: rnd_tasks -> rnd_count -> rnd_select (bg_random_kernels.h).  emit_kernel serves the ordered enumerate API.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -662,26 +663,130 @@ static thread_local std::string g_hip_err;
         HIPCHK(hipSetDevice((env)->device));             \
     } while (0)
 
-struct bgamd_env {
-    int device = 0;
-    EnvView v{};
-    StagedView sv{};
-    RandomView rv{};
-    float *d_w[2] = {nullptr, nullptr};    // raw weights 25601, two slots (head-to-head: one per side)
+namespace {
+// The value net's device tables: per weight slot (head-to-head: one per side) the raw weights and every layout of W1 a kernel reads,
+// and the two count LUTs.  NET_TABLES is the one list of them: allocation and freeing walk it, and an env that borrows another's
+// tables (scratch_env) takes them by assigning the struct.
+struct NetTables {
+    float *d_w[2] = {nullptr, nullptr};    // raw weights 25601
     float4 *d_wl[2] = {nullptr, nullptr};  // fp32 MFMA layout [99][64]
     float4 *d_wt[2] = {nullptr, nullptr};  // W1^T [198][132] for the incremental evaluator
     uint4 *d_wm[2] = {nullptr, nullptr};   // W1^T as f16 hi | lo dwords [198][4][32] for the MFMA delta kernel (bg_eval_mfma.h)
-    bool wm_ok[2] = {false, false};        // the slot's table fits f16 (else the VALU delta kernel evaluates that slot)
-    bool mfma_delta = false;               // BGAMD_MFMA_DELTA=1: eval_rows_mdelta_kernel instead of eval_rows_delta_kernel
     uint4 *d_wl3[2] = {nullptr, nullptr};  // bf16 hi | mid | lo split, bf16 MFMA layout x 3 (root term, rounds 1-4; -DBG_ROOT_F16X2=0)
     uint4 *d_wr2[2] = {nullptr, nullptr};  // f16 hi | lo split in the same layout (the root pass, bg_root_resident.h)
     uint4 *d_wl16[2] = {nullptr, nullptr}; // bf16 MFMA layout [13][4][64] x 8 bf16
     uint4 *d_wlx2[2] = {nullptr, nullptr}; // f16 hi | lo split, same layout twice
     uint4 *d_wd16[2] = {nullptr, nullptr}; // the same split with -log2(e) and b1 folded in: the register-resident dense kernel (bg_eval_dense16.h)
-    bool d16 = false;                      // BGAMD_F16X2_RESIDENT=1: eval_rows_d16_kernel (W1 resident in registers) for BGAMD_F16X2 -- measured 6 % slower than round 1's eval_rows_f16x2_kernel
     uint2 *d_lut = nullptr;                // count -> 4 bf16 features
     uint2 *d_lut16 = nullptr;              // count -> 4 f16 features
+    bool wm_ok[2] = {false, false};        // the slot's d_wm fits f16 (else the VALU delta kernel evaluates that slot)
     bool has_weights[2] = {false, false};
+    const float *b1(int slot) const { return d_w[slot] + N_HID * N_IN; }      // the fp32 tail of the raw weights: b1 [N_HID], W2 [N_HID], b2 [1]
+    const float *w2(int slot) const { return b1(slot) + N_HID; }
+    const float *b2(int slot) const { return w2(slot) + N_HID; }
+    const uint4 *root_w(int slot) const { return ROOT_F16X2 ? d_wr2[slot] : d_wl3[slot]; }    // the root pass's W1 planes and LUT (bg_root_resident.h)
+    const uint2 *root_lut() const { return ROOT_F16X2 ? d_lut16 : d_lut; }
+};
+// (member, pointers in it, bytes of device memory behind each).  Every member above is an array of plain device pointers (or one), so the
+// walk below treats each as void *[count].  A new table needs its member above AND its line here: one left out of this list is never
+// allocated and stays null, which its first kernel trips over at once -- not a stale copy, not a double free.  d_wm and d_wd16 are
+// members in both builds but listed, and so allocated, in the experimental build only: its kernels are their only readers.
+static const struct { size_t offset; int count; size_t bytes; } NET_TABLES[] = {
+    {offsetof(NetTables, d_w), 2, N_PARAMS * 4},           {offsetof(NetTables, d_wl), 2, EVAL_LDS_BYTES},
+    {offsetof(NetTables, d_wt), 2, DELTA_W_FLOATS * 4},    {offsetof(NetTables, d_wl3), 2, 3 * EVAL16_W_BYTES},
+    {offsetof(NetTables, d_wr2), 2, 2 * EVAL16_W_BYTES},   {offsetof(NetTables, d_wl16), 2, EVAL16_W_BYTES},
+    {offsetof(NetTables, d_wlx2), 2, EVAL16X2_W_BYTES},    {offsetof(NetTables, d_lut16), 1, EVAL16_LUT_BYTES},
+    {offsetof(NetTables, d_lut), 1, EVAL16_LUT_BYTES},
+#ifdef BGAMD_EXPERIMENTAL
+    {offsetof(NetTables, d_wm), 2, MD_W_BYTES},            {offsetof(NetTables, d_wd16), 2, EVAL16X2_W_BYTES},
+#endif
+};
+// allocate (fresh tables) or free them all, and forget them
+static int net_tables(NetTables &t, bool allocate)
+{
+    for (const auto &d : NET_TABLES)
+        for (void **p = (void **)((char *)&t + d.offset), **end = p + d.count; p < end; ++p) {
+            if (allocate) HIPCHK(hipMalloc(p, d.bytes));
+            else if (*p) hipFree(*p);
+        }
+    if (!allocate) t = NetTables{};
+    return BGAMD_OK;
+}
+
+// Buffers that grow on demand: `need` elements of elem_bytes each in every one of bufs (freed and allocated anew when cap is below it)
+using BufList = std::initializer_list<std::pair<void **, size_t>>;      // (pointer, bytes per element)
+static int alloc_buffers(long long n, BufList bufs) { for (auto &b : bufs) HIPCHK(hipMalloc(b.first, (size_t)n * b.second)); return BGAMD_OK; }
+static int grow_buffers(long long need, long long &cap, BufList bufs)
+{
+    if (need <= cap) return BGAMD_OK;
+    for (auto &b : bufs) { if (*b.first) HIPCHK(hipFree(*b.first)); *b.first = nullptr; }
+    cap = 0;
+    if (int rc = alloc_buffers(need, bufs)) return rc;
+    cap = need;
+    return BGAMD_OK;
+}
+static void free_all(std::initializer_list<void *> ptrs) { for (void *p : ptrs) if (p) hipFree(p); }
+
+// 2-ply search (bgamd_env_step_search, bg_search.h)
+struct SearchState {
+    uint32_t *cnt = nullptr, *off = nullptr, *fill = nullptr, *kept = nullptr, *koff = nullptr, *max = nullptr;  // per game (+1)
+    uint32_t *grp = nullptr;               // [cap_rows] row indices grouped by game
+    int32_t *rank = nullptr;               // [cap_rows]
+    uint4 *c_rows = nullptr;               // candidates [c_cap][2]
+    uint32_t *c_key = nullptr;
+    float *c_v1 = nullptr, *c_v2 = nullptr, *c_rval = nullptr;     // c_rval [c_cap][21]
+    long long c_cap = 0;
+    int k = -1;                            // K of the last search step (-1: none yet)
+    void release() { free_all({cnt, off, fill, kept, koff, max, grp, rank, c_rows, c_key, c_v1, c_v2, c_rval}); *this = SearchState{}; }
+};
+
+// Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h), and what the luck-adjusted ones add (bg_vr.h)
+struct RolloutState {
+    uint4 *pos = nullptr, *fan = nullptr, *trows = nullptr;        // [cap_pos], [cap_fan], [cap_lanes]
+    float *fval = nullptr, *tval = nullptr, *tv = nullptr;         // [cap_fan], [cap_trials], [cap_lanes]
+    uint32_t *tturns = nullptr, *lane = nullptr, *tids = nullptr;  // [cap_trials], [cap_lanes], [cap_lanes]
+    long long cap_pos = 0, cap_fan = 0, cap_trials = 0, cap_lanes = 0;
+    unsigned long long *host = nullptr;    // pinned, [2][4] (done, truncated, rollout error bits, env error bits) of the last two reads
+    hipEvent_t ev[2] = {nullptr, nullptr}; // ... and the event behind each of the two
+    int64_t info[4] = {0, 0, 0, 0};        // bgamd_env_rollout_info
+    double *tluck = nullptr, *m0 = nullptr;                        // tluck [P T] luck totals, m0 [P] / f0 [P][21]: turn 0 (rotation)
+    float *vf = nullptr, *f0 = nullptr;                            // vf [L][21]: the trial lanes' f of the turn at hand
+    long long cap_vtrials = 0, cap_vlanes = 0, cap_vpos = 0;
+    long long vr_P = 0, vr_T = 0;          // P, T of the last rollout if it had BGAMD_ROLLOUT_VR (0: bgamd_env_rollout_vr_read refuses)
+    int read_back_ready()                  // the pinned words and the two events, created on first use
+    {
+        if (!host) HIPCHK(hipHostMalloc(&host, 8 * 8));
+        for (hipEvent_t &e : ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return BGAMD_OK;
+    }
+    void release()
+    {
+        free_all({pos, fan, trows, fval, tval, tv, tturns, lane, tids, tluck, m0, vf, f0});
+        if (host) hipHostFree(host);
+        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+        *this = RolloutState{};
+    }
+};
+
+// pre-roll evaluation (bgamd_env_evaluate_preroll, bg_vr.h)
+struct PrerollState {
+    uint4 *rows = nullptr;                 // [cap] the positions
+    float *f = nullptr;                    // [cap][21]
+    long long cap = 0;
+    void release() { free_all({rows, f}); *this = PrerollState{}; }
+};
+
+enum { A_INTAKE = RO_CTRS, A_WORDS = RO_CTRS + 2 };      // bgamd_env::a_ctr
+}  // namespace
+
+struct bgamd_env {
+    int device = 0;
+    EnvView v{};
+    StagedView sv{};
+    RandomView rv{};
+    NetTables net;                         // the value net's device tables (a scratch env: its parent's, see scratch_env)
+    bool mfma_delta = false;               // BGAMD_MFMA_DELTA=1: eval_rows_mdelta_kernel instead of eval_rows_delta_kernel
+    bool d16 = false;                      // BGAMD_F16X2_RESIDENT=1: eval_rows_d16_kernel (W1 resident in registers) for BGAMD_F16X2 -- measured 6 % slower than round 1's eval_rows_f16x2_kernel
     int n_cu = 256;
     hipStream_t side = nullptr;            // second stream: the root pass of the value net runs beside the doubles plies
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;   //   (fork after roots_kernel, join before the incremental kernel)
@@ -720,36 +825,16 @@ struct bgamd_env {
     size_t ev_used = 0;
     double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // 2-ply search (bgamd_env_step_search, bg_search.h).  scratch: the env whose lanes are the virtual roots of a chunk, created on
-    // first use and grown up to SEARCH_CHUNK lanes; it borrows this env's weight tables (borrows_weights: not its to free)
-    bgamd_env *scratch = nullptr;
+    // The analysis features run the greedy step's kernels on internal envs (scratch_env): `scratch` holds the virtual roots the 2-ply search
+    // and the pre-roll evaluation score, `rscratch` plays the rollout's trials.  Such an env borrows_weights: its `net` is its parent's.
+    bgamd_env *scratch = nullptr, *rscratch = nullptr;
     bool borrows_weights = false;
-    uint32_t *s_cnt = nullptr, *s_off = nullptr, *s_fill = nullptr, *s_kept = nullptr, *s_koff = nullptr, *s_max = nullptr;  // per game (+1)
-    uint32_t *s_grp = nullptr;             // [cap_rows] row indices grouped by game
-    int32_t *s_rank = nullptr;             // [cap_rows]
-    uint4 *c_rows = nullptr;               // candidates [c_cap][2]
-    uint32_t *c_key = nullptr;
-    float *c_v1 = nullptr, *c_v2 = nullptr, *c_rval = nullptr;     // c_rval [c_cap][21]
-    long long c_cap = 0;
-    int search_k = -1;                     // K of the last search step (-1: none yet)
-    // Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h).  rscratch: the env whose lanes play the trials, created on first use with
-    // the call's lane count (re-created when it differs); it borrows this env's weight tables as the search's scratch env does
-    bgamd_env *rscratch = nullptr;
-    uint4 *r_pos = nullptr, *r_fan = nullptr, *r_trows = nullptr;
-    float *r_fval = nullptr, *r_tval = nullptr, *r_tv = nullptr;
-    uint32_t *r_tturns = nullptr, *r_lane = nullptr, *r_tids = nullptr;
-    unsigned long long *r_ctr = nullptr, *r_host = nullptr;        // r_host: pinned, [2][2] (done, error bits) of the last two reads
-    long long r_cap_pos = 0, r_cap_fan = 0, r_cap_trials = 0, r_cap_lanes = 0;
-    int64_t r_info[4] = {0, 0, 0, 0};      // bgamd_env_rollout_info
-    // pre-roll evaluation and luck-adjusted rollouts (bg_vr.h): both score their (position, roll) roots on the search's scratch env
-    uint4 *p_rows = nullptr;
-    float *p_f = nullptr;
-    unsigned long long *p_ctr = nullptr;
-    long long p_cap = 0;
-    double *r_tluck = nullptr, *r_m0 = nullptr;                     // r_tluck [P T] luck totals, r_m0 [P] / r_f0 [P][21]: turn 0 (rotation)
-    float *r_vf = nullptr, *r_f0 = nullptr;                         // r_vf [L][21]: the trial lanes' f of the turn at hand
-    long long r_cap_vtrials = 0, r_cap_vlanes = 0, r_cap_vpos = 0;
-    long long r_vr_P = 0, r_vr_T = 0;      // P, T of the last rollout if it had BGAMD_ROLLOUT_VR (0: bgamd_env_rollout_vr_read refuses)
+    // [A_WORDS]: the rollout's counters (RoView::ctr), then the word that takes the bad-state bit of intake_positions -- one allocation, a
+    // whole number of 16-byte units, so that the rollout's one fill launch clears both.  48 bytes, allocated with every env (env_allocate).
+    unsigned long long *a_ctr = nullptr;
+    SearchState srch;
+    RolloutState ro;
+    PrerollState pre;
 };
 
 namespace {
@@ -844,7 +929,7 @@ int bgamd_env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed
     return env_create(out, n_games, device, seed, lane_offset, lane_stride, arena_rows, false);
 }
 
-// borrows_weights: the search's scratch env -- no weight tables of its own, the parent's are pointed at before every use
+// borrows_weights: a scratch env (scratch_env) -- no weight tables of its own, the parent's are assigned to it before every use
 static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
                       int64_t arena_rows, bool borrows_weights)
 {
@@ -927,38 +1012,15 @@ static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t
     if (cap > (1ll << 31) - 64) cap = (1ll << 31) - 64;
     v.cap = cap;
     const size_t n = (size_t)n_games;
-    HIPCHK(hipMalloc(&v.planes, n * 8 * 4));
-    HIPCHK(hipMalloc(&v.meta, n * 4));
-    HIPCHK(hipMalloc(&v.ply, n * 4));
-    HIPCHK(hipMalloc(&v.episode, n * 4));
-    HIPCHK(hipMalloc(&v.flags, n * 4));
-    HIPCHK(hipMalloc(&v.cand_off, n * 4));
-    HIPCHK(hipMalloc(&v.cand_cnt, n * 4));
-    HIPCHK(hipMalloc(&v.chosen, n * 4));
-    HIPCHK(hipMalloc(&v.chosen_seq, n * 4));
-    HIPCHK(hipMalloc(&v.chosen_val, n * 4));
-    HIPCHK(hipMalloc(&v.rows, (size_t)cap * 32));
-    HIPCHK(hipMalloc(&v.seqs, (size_t)cap * 4));
-    HIPCHK(hipMalloc(&v.values, (size_t)cap * 4));
+    if (int rc = alloc_buffers(n_games, {{(void **)&v.planes, 8 * 4}, {(void **)&v.meta, 4}, {(void **)&v.ply, 4}, {(void **)&v.episode, 4},   // per lane
+                                        {(void **)&v.flags, 4}, {(void **)&v.cand_off, 4}, {(void **)&v.cand_cnt, 4}, {(void **)&v.chosen, 4},
+                                        {(void **)&v.chosen_seq, 4}, {(void **)&v.chosen_val, 4}})) return rc;
+    if (int rc = alloc_buffers(cap, {{(void **)&v.rows, 32}, {(void **)&v.seqs, 4}, {(void **)&v.values, 4}})) return rc;                  // per arena row
     HIPCHK(hipMalloc(&v.counters, C_COUNT * 8));
-    for (int k = 0; k < 2 && !env->borrows_weights; ++k) {
-        HIPCHK(hipMalloc(&env->d_w[k], N_PARAMS * 4));
-        HIPCHK(hipMalloc(&env->d_wl[k], EVAL_LDS_BYTES));
-        HIPCHK(hipMalloc(&env->d_wt[k], DELTA_W_FLOATS * 4));
-#ifdef BGAMD_EXPERIMENTAL
-        HIPCHK(hipMalloc(&env->d_wm[k], MD_W_BYTES));
-#endif
-        HIPCHK(hipMalloc(&env->d_wl3[k], 3 * EVAL16_W_BYTES));
-        HIPCHK(hipMalloc(&env->d_wr2[k], 2 * EVAL16_W_BYTES));
-        HIPCHK(hipMalloc(&env->d_wl16[k], EVAL16_W_BYTES));
-        HIPCHK(hipMalloc(&env->d_wlx2[k], EVAL16X2_W_BYTES));
-#ifdef BGAMD_EXPERIMENTAL
-        HIPCHK(hipMalloc(&env->d_wd16[k], EVAL16X2_W_BYTES));
-#endif
-    }
-    if (!env->borrows_weights) HIPCHK(hipMalloc(&env->d_lut16, EVAL16_LUT_BYTES));
+    HIPCHK(hipMalloc(&env->a_ctr, A_WORDS * 8));
+    if (!env->borrows_weights)
+        if (int rc = net_tables(env->net, true)) return rc;
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_f16x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL16X2_LDS_TOTAL));
-    if (!env->borrows_weights) HIPCHK(hipMalloc(&env->d_lut, EVAL16_LUT_BYTES));
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL16_LDS_TOTAL));
     {   // staged greedy step (bg_staged.h): node lists, per-workgroup staging, unique arena
         StagedView &sv = env->sv;
@@ -1015,28 +1077,15 @@ int bgamd_env_destroy(bgamd_env *env)
     if (env->scratch) bgamd_env_destroy(env->scratch);
     if (env->rscratch) bgamd_env_destroy(env->rscratch);
     HIPCHK(hipSetDevice(env->device));
-    if (env->borrows_weights) {                  // the parent's tables: not ours to free
-        for (int k = 0; k < 2; ++k) {
-            env->d_w[k] = nullptr; env->d_wl[k] = nullptr; env->d_wt[k] = nullptr; env->d_wm[k] = nullptr; env->d_wl3[k] = nullptr;
-            env->d_wr2[k] = nullptr; env->d_wl16[k] = nullptr; env->d_wlx2[k] = nullptr; env->d_wd16[k] = nullptr;
-        }
-        env->d_lut = nullptr; env->d_lut16 = nullptr;
-    }
-    {
-        void *sp[] = {env->s_cnt, env->s_off, env->s_fill, env->s_kept, env->s_koff, env->s_max, env->s_grp, env->s_rank, env->c_rows,
-                      env->c_key, env->c_v1, env->c_v2, env->c_rval, env->r_pos, env->r_fan, env->r_trows, env->r_fval, env->r_tval,
-                      env->r_tv, env->r_tturns, env->r_lane, env->r_tids, env->r_ctr, env->p_rows, env->p_f, env->p_ctr,
-                      env->r_tluck, env->r_m0, env->r_vf, env->r_f0};
-        for (void *p : sp) if (p) hipFree(p);
-        if (env->r_host) hipHostFree(env->r_host);
-    }
-    EnvView &v = env->v;
-    void *ptrs[] = {v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq,
-                    v.chosen_val, v.rows, v.seqs, v.values, v.counters, env->d_w[0], env->d_wl[0], env->d_wl16[0], env->d_w[1], env->d_wl[1], env->d_wl16[1], env->d_lut, env->d_wlx2[0], env->d_wlx2[1], env->d_wd16[0], env->d_wd16[1], env->d_lut16, env->d_wt[0], env->d_wt[1], env->d_wm[0], env->d_wm[1], env->d_wl3[0], env->d_wl3[1], env->d_wr2[0], env->d_wr2[1], env->sv.root_rows, env->sv.root_hidden,
-                    env->sv.d1, env->sv.d2, env->sv.f, env->sv.f2, env->sv.u_rows, env->sv.u_info, env->sv.best, env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n};
-    for (void *p : ptrs) if (p) hipFree(p);
-    if (env->d_scalar) hipFree(env->d_scalar);
-    if (env->d_tmp) hipFree(env->d_tmp);
+    if (!env->borrows_weights) net_tables(env->net, false);        // (a scratch env's are its parent's)
+    env->srch.release();
+    env->ro.release();
+    env->pre.release();
+    const EnvView &v = env->v;
+    const StagedView &sv = env->sv;
+    free_all({v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq, v.chosen_val, v.rows, v.seqs,
+              v.values, v.counters, env->a_ctr, sv.root_rows, sv.root_hidden, sv.d1, sv.d2, sv.f, sv.f2, sv.u_rows, sv.u_info, sv.best,
+              env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n, env->d_scalar, env->d_tmp});
     for (hipEvent_t e : env->ev) hipEventDestroy(e);
     if (env->ev_fork) hipEventDestroy(env->ev_fork);
     if (env->ev_join) hipEventDestroy(env->ev_join);
@@ -1359,84 +1408,101 @@ int bgamd_env_load_weights_slot(bgamd_env *env, int slot, const float *h_weights
     std::vector<float> wl((size_t)K_STEPS * 64 * 4);
     relayout_w1_f32(h_weights, wl.data());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(env->d_w[slot], h_weights, N_PARAMS * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(env->d_wl[slot], wl.data(), EVAL_LDS_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_w[slot], h_weights, N_PARAMS * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wl[slot], wl.data(), EVAL_LDS_BYTES, hipMemcpyHostToDevice));
     std::vector<float> wt((size_t)DELTA_W_FLOATS);
     relayout_w1_delta(h_weights, wt.data());
-    HIPCHK(hipMemcpy(env->d_wt[slot], wt.data(), DELTA_W_FLOATS * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wt[slot], wt.data(), DELTA_W_FLOATS * 4, hipMemcpyHostToDevice));
 #ifdef BGAMD_EXPERIMENTAL
     std::vector<uint32_t> wmd((size_t)MD_W_DWORDS);
-    env->wm_ok[slot] = relayout_w1_mdelta(h_weights, wmd.data()) >= 0;
-    HIPCHK(hipMemcpy(env->d_wm[slot], wmd.data(), MD_W_BYTES, hipMemcpyHostToDevice));
+    env->net.wm_ok[slot] = relayout_w1_mdelta(h_weights, wmd.data()) >= 0;
+    HIPCHK(hipMemcpy(env->net.d_wm[slot], wmd.data(), MD_W_BYTES, hipMemcpyHostToDevice));
 #endif
     std::vector<uint16_t> wl3((size_t)3 * K16_STEPS * 4 * 64 * 8);
     relayout_w1_bf16x3(h_weights, wl3.data());
-    HIPCHK(hipMemcpy(env->d_wl3[slot], wl3.data(), 3 * EVAL16_W_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wl3[slot], wl3.data(), 3 * EVAL16_W_BYTES, hipMemcpyHostToDevice));
     relayout_w1_f16x2_root(h_weights, wl3.data());
-    HIPCHK(hipMemcpy(env->d_wr2[slot], wl3.data(), 2 * EVAL16_W_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wr2[slot], wl3.data(), 2 * EVAL16_W_BYTES, hipMemcpyHostToDevice));
     std::vector<uint16_t> wl16((size_t)K16_STEPS * 4 * 64 * 8);
     relayout_w1_bf16(h_weights, wl16.data());
     uint32_t lut[32];
     make_count_lut(lut);
-    HIPCHK(hipMemcpy(env->d_wl16[slot], wl16.data(), EVAL16_W_BYTES, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(env->d_lut, lut, EVAL16_LUT_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wl16[slot], wl16.data(), EVAL16_W_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_lut, lut, EVAL16_LUT_BYTES, hipMemcpyHostToDevice));
     std::vector<uint16_t> wx2((size_t)2 * K16_STEPS * 4 * 64 * 8);
     relayout_w1_f16x2(h_weights, wx2.data());
     make_count_lut_f16(lut);
-    HIPCHK(hipMemcpy(env->d_wlx2[slot], wx2.data(), EVAL16X2_W_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wlx2[slot], wx2.data(), EVAL16X2_W_BYTES, hipMemcpyHostToDevice));
 #ifdef BGAMD_EXPERIMENTAL
     relayout_w1_d16(h_weights, wx2.data());
-    HIPCHK(hipMemcpy(env->d_wd16[slot], wx2.data(), EVAL16X2_W_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(env->net.d_wd16[slot], wx2.data(), EVAL16X2_W_BYTES, hipMemcpyHostToDevice));
 #endif
-    HIPCHK(hipMemcpy(env->d_lut16, lut, EVAL16_LUT_BYTES, hipMemcpyHostToDevice));
-    env->has_weights[slot] = true;
+    HIPCHK(hipMemcpy(env->net.d_lut16, lut, EVAL16_LUT_BYTES, hipMemcpyHostToDevice));
+    env->net.has_weights[slot] = true;
     return BGAMD_OK;
 }
 
 static int launch_eval(bgamd_env *env, int slot, int precision, const unsigned long long *n_rows_ptr, long long n_rows_imm,
                        const uint4 *rows, float *values, const uint2 *info, unsigned long long *best, hipStream_t s)
 {
-    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
     if (precision != BGAMD_F32 && precision != BGAMD_BF16 && precision != BGAMD_F16X2 && precision != BGAMD_F32_DENSE)
         return BGAMD_E_INVALID;
-    const float *b1 = env->d_w[slot] + N_HID * N_IN, *w2 = b1 + N_HID, *b2 = w2 + N_HID;
+    const NetTables &t = env->net;
+    const float *b1 = t.b1(slot), *w2 = t.w2(slot), *b2 = t.b2(slot);
+    unsigned long long *rows_ctr = n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : nullptr, *ksteps = n_rows_ptr ? &env->v.counters[C_KSTEPS] : nullptr;
     // every workgroup first stages W1 in LDS: no more workgroups than the rows can use (a greedy step averages ~18
     // rows per game; more than the estimate only means more tiles per wave)
     const long long est_rows = n_rows_ptr ? env->v.n * 24 : n_rows_imm;
     long long eb = (est_rows + (EVAL_THREADS / 64) * 32 - 1) / ((EVAL_THREADS / 64) * 32);
     eb = eb < 1 ? 1 : (eb > env->n_cu ? env->n_cu : eb);
     const dim3 egrid((unsigned)eb);
+    KTimer timer(env, s, 1);
 #ifdef BGAMD_EXPERIMENTAL
     if (precision == BGAMD_F16X2 && env->d16) {
-        KTimer t(env, s, 1);
         long long tiles = (est_rows + 31) / 32;
         const long long per_cu = BG_D16_WAVES;                                                     // 4-wave workgroups per CU
         long long wg = tiles < 1 ? 1 : (tiles > per_cu * env->n_cu ? per_cu * env->n_cu : tiles);
-        hipLaunchKernelGGL(eval_rows_d16_kernel<2>, dim3((unsigned)wg), dim3(D16_THREADS), D16_LDS_BYTES, s, rows, n_rows_ptr,
-                           n_rows_imm, n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : (unsigned long long *)nullptr,
-                           (const uint4 *)env->d_wd16[slot], (const uint2 *)env->d_lut16, w2, b2, values, info, best,
-                           n_rows_ptr ? &env->v.counters[C_KSTEPS] : (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0);
+        hipLaunchKernelGGL(eval_rows_d16_kernel<2>, dim3((unsigned)wg), dim3(D16_THREADS), D16_LDS_BYTES, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
+                           (const uint4 *)t.d_wd16[slot], (const uint2 *)t.d_lut16, w2, b2, values, info, best, ksteps, (unsigned long long *)nullptr, 0);
     } else
 #endif
-    if (precision == BGAMD_F16X2) {
-        KTimer t(env, s, 1);
-        hipLaunchKernelGGL(eval_rows_f16x2_kernel, egrid, dim3(EVAL_THREADS), EVAL16X2_LDS_TOTAL, s, rows, n_rows_ptr,
-                           n_rows_imm, n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : (unsigned long long *)nullptr,
-                           (const uint4 *)env->d_wlx2[slot], (const uint2 *)env->d_lut16, b1, w2, b2, values, info, best);
-    } else if (precision == BGAMD_BF16) {
-        KTimer t(env, s, 1);
-        hipLaunchKernelGGL(eval_rows_bf16_kernel, egrid, dim3(EVAL_THREADS), EVAL16_LDS_TOTAL, s, rows, n_rows_ptr,
-                           n_rows_imm, n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : (unsigned long long *)nullptr,
-                           (const uint4 *)env->d_wl16[slot], (const uint2 *)env->d_lut, b1, w2, b2, values, info, best);
-    } else {
-        KTimer t(env, s, 1);
-        hipLaunchKernelGGL(eval_rows_f32_kernel<false>, egrid, dim3(EVAL_THREADS), EVAL_LDS_TOTAL, s, rows, n_rows_ptr,
-                           n_rows_imm, n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : (unsigned long long *)nullptr,
-                           (const float4 *)env->d_wl[slot], b1, w2, b2, values, info, best,
-                           n_rows_ptr ? &env->v.counters[C_KSTEPS] : (unsigned long long *)nullptr);
-    }
+    if (precision == BGAMD_F16X2)
+        hipLaunchKernelGGL(eval_rows_f16x2_kernel, egrid, dim3(EVAL_THREADS), EVAL16X2_LDS_TOTAL, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
+                           (const uint4 *)t.d_wlx2[slot], (const uint2 *)t.d_lut16, b1, w2, b2, values, info, best);
+    else if (precision == BGAMD_BF16)
+        hipLaunchKernelGGL(eval_rows_bf16_kernel, egrid, dim3(EVAL_THREADS), EVAL16_LDS_TOTAL, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
+                           (const uint4 *)t.d_wl16[slot], (const uint2 *)t.d_lut, b1, w2, b2, values, info, best);
+    else
+        hipLaunchKernelGGL(eval_rows_f32_kernel<false>, egrid, dim3(EVAL_THREADS), EVAL_LDS_TOTAL, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
+                           (const float4 *)t.d_wl[slot], b1, w2, b2, values, info, best, ksteps);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
+}
+
+// The incremental value net's root pass: hidden[n][N_HID] = W1 x + b1 of the n root rows (one dense product per GAME).  f32_chain: the
+// caller honours BGAMD_ROOT_F32 (experimental build)
+static void launch_root_pass(bgamd_env *env, int slot, const uint4 *rows, long long n, float *hidden, [[maybe_unused]] bool f32_chain, hipStream_t s)
+{
+    const NetTables &t = env->net;
+#ifdef BGAMD_EXPERIMENTAL
+    if (f32_chain && env->root_f32_mfma)
+        hipLaunchKernelGGL(eval_rows_f32_kernel<true>, dim3(env->n_cu), dim3(EVAL_THREADS), EVAL_LDS_TOTAL, s, rows,
+                           (const unsigned long long *)nullptr, n, (unsigned long long *)nullptr, (const float4 *)t.d_wl[slot], t.b1(slot),
+                           t.w2(slot), t.b2(slot), hidden, (const uint2 *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+    else if (!env->root_resident) {
+        long long blocks = ((n + 31) / 32 + ROOT3_THREADS / 64 - 1) / (ROOT3_THREADS / 64);
+        if (blocks > env->n_cu) blocks = env->n_cu;
+        hipLaunchKernelGGL(root_hidden_bf16x3_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOT3_THREADS), ROOT3_LDS_TOTAL, s, rows, n,
+                           (const uint4 *)t.d_wl3[slot], (const uint2 *)t.d_lut, t.b1(slot), hidden);
+    } else
+#endif
+    {
+        long long blocks = (n + 31) / 32;
+        if (blocks > 2ll * env->n_cu) blocks = 2ll * env->n_cu;                 // two 4-wave workgroups per CU (256 VGPRs each wave)
+        hipLaunchKernelGGL(root_hidden_resident_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOTR_THREADS), ROOTR_LDS_BYTES, s, rows, n,
+                           t.root_w(slot), t.root_lut(), t.b1(slot), hidden);
+    }
 }
 
 }  // extern "C"
@@ -1463,16 +1529,17 @@ struct GreedyRun {
     EnvView ev;                            // the env's view as this run's launches take it (ring log: the slots of the step at hand)
     long long cur_step = 0;                // ring log: the env step being played
     bool root_ready = false;               // the boundary launch of the step before has already run this step's root pass
+    bool first_of_run = true;              // no step since begin() (read by the BG_ABL_STEP timing ablation only)
     const float *b1, *w2, *b2;
 
     int init(bgamd_env *e, int fl, float eps, int prec)
     {
         env = e; flags = fl; epsilon = eps; precision = prec;
         slot = (fl & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
-        if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+        if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
         if (prec != BGAMD_F32 && prec != BGAMD_BF16 && prec != BGAMD_F16X2 && prec != BGAMD_F32_DENSE) return BGAMD_E_INVALID;
         incremental = prec == BGAMD_F32;
-        b1 = env->d_w[slot] + N_HID * N_IN; w2 = b1 + N_HID; b2 = w2 + N_HID;
+        b1 = env->net.b1(slot); w2 = env->net.w2(slot); b2 = env->net.b2(slot);
         sv = env->sv;
         sv.tops = env->tops_base;
         // two row arenas (by class) for the incremental value net; the other value-net kernels read one
@@ -1498,7 +1565,7 @@ struct GreedyRun {
             sv.shards = (env->expand_merged && env->list_shards && nd % LIST_SHARDS == 0 && nl % LIST_SHARDS == 0) ? LIST_SHARDS : 1;
         }
 #ifdef BGAMD_EXPERIMENTAL
-        if (env->mfma_delta && env->wm_ok[slot]) sv.b_base = 0;
+        if (env->mfma_delta && env->net.wm_ok[slot]) sv.b_base = 0;
 #endif
         parity = 0;
         root_ready = false;
@@ -1535,15 +1602,22 @@ struct GreedyRun {
         KTimer t(env, s, 4);
         next_log_slot();
         hipLaunchKernelGGL(roots_kernel, grid1(env->v.n, LANE_NT), dim3(LANE_NT), 0, s, ev, sv, flags);
+        first_of_run = true;
         return BGAMD_OK;
     }
-    // score_only (the 2-ply search, bg_search.h): roots, expansion and value net only -- no apply launch, sv.best is left for the caller
-    int step(const StepStreams &ss, bool more, bool first_of_run = true, bool score_only = false)
+    // The lanes of e as they stand, scored and not moved (the 2-ply search, the pre-roll evaluation): one greedy step's roots, expansion
+    // and incremental value net with the weights of fl's slot on stream s, no apply launch -- e->sv.best and root_hidden are the caller's
+    int score(bgamd_env *e, int fl, hipStream_t s)
     {
-        (void)first_of_run;
+        int rc;
+        if ((rc = init(e, fl, 0.0f, BGAMD_F32)) || (rc = begin(s))) return rc;
+        return step(StepStreams{s, s, e->n_cu}, false, true);
+    }
+    int step(const StepStreams &ss, bool more, bool score_only = false)
+    {
         const long long n = env->v.n;
         hipStream_t s = ss.gen;
-        env->choice[0] = incremental ? ((env->mfma_delta && env->wm_ok[slot]) ? 1 : 0)
+        env->choice[0] = incremental ? ((env->mfma_delta && env->net.wm_ok[slot]) ? 1 : 0)
                                      : (precision == BGAMD_F32_DENSE ? 2 : precision == BGAMD_F16X2 ? (env->d16 ? 4 : 3) : 5);
         const bool own_root_launch = incremental && !root_ready;
         env->choice[2] = ((own_root_launch && ss.root != s) ? 1 : 0) | (env->expand_merged ? 2 : 0);
@@ -1562,27 +1636,7 @@ struct GreedyRun {
 #endif
             {
                 KTimer t(env, s2, 6);
-#ifdef BGAMD_EXPERIMENTAL
-                if (env->root_f32_mfma)
-                    hipLaunchKernelGGL(eval_rows_f32_kernel<true>, dim3(ss.n_cu), dim3(EVAL_THREADS), EVAL_LDS_TOTAL, s2,
-                                       (const uint4 *)sv.root_rows, (const unsigned long long *)nullptr, n, (unsigned long long *)nullptr,
-                                       (const float4 *)env->d_wl[slot], b1, w2, b2, sv.root_hidden, (const uint2 *)nullptr,
-                                       (unsigned long long *)nullptr, (unsigned long long *)nullptr);
-                else if (!env->root_resident) {
-                    long long blocks = ((n + 31) / 32 + ROOT3_THREADS / 64 - 1) / (ROOT3_THREADS / 64);
-                    if (blocks > ss.n_cu) blocks = ss.n_cu;
-                    hipLaunchKernelGGL(root_hidden_bf16x3_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOT3_THREADS),
-                                       ROOT3_LDS_TOTAL, s2, (const uint4 *)sv.root_rows, n, (const uint4 *)env->d_wl3[slot],
-                                       (const uint2 *)env->d_lut, b1, sv.root_hidden);
-                } else
-#endif
-                {
-                    long long blocks = (n + 31) / 32;
-                    if (blocks > 2ll * ss.n_cu) blocks = 2ll * ss.n_cu;                 // two 4-wave workgroups per CU (256 VGPRs each wave)
-                    hipLaunchKernelGGL(root_hidden_resident_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOTR_THREADS),
-                                       ROOTR_LDS_BYTES, s2, (const uint4 *)sv.root_rows, n, (const uint4 *)(ROOT_F16X2 ? env->d_wr2[slot] : env->d_wl3[slot]),
-                                       (const uint2 *)(ROOT_F16X2 ? env->d_lut16 : env->d_lut), b1, sv.root_hidden);
-                }
+                launch_root_pass(env, slot, (const uint4 *)sv.root_rows, n, sv.root_hidden, true, s2);
             }
             if (s2 != s) HIPCHK(hipEventRecord(env->ev_join, s2));
         }
@@ -1620,10 +1674,10 @@ struct GreedyRun {
             long long dblocks = (n * 24 + DELTA_THREADS - 1) / DELTA_THREADS;
             dblocks = dblocks < 1 ? 1 : (dblocks > ss.n_cu ? ss.n_cu : dblocks);
 #ifdef BGAMD_EXPERIMENTAL
-            if (env->mfma_delta && env->wm_ok[slot])
+            if (env->mfma_delta && env->net.wm_ok[slot])
                 hipLaunchKernelGGL(eval_rows_mdelta_kernel, dim3((unsigned)dblocks), dim3(MD_THREADS), MD_LDS_TOTAL, se,
                                    (const uint4 *)sv.u_rows, (const unsigned long long *)&sv.tops[T_U], (long long)sv.cap_rows, &env->v.counters[C_ROWS_EVAL],
-                                   (const uint4 *)env->d_wm[slot], w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden,
+                                   (const uint4 *)env->net.d_wm[slot], w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden,
                                    env->v.values, (const uint2 *)sv.u_info, sv.best, &env->v.counters[C_KSTEPS],
                                    fused ? sv_next.tops : (unsigned long long *)nullptr, (int)T_COUNT, &env->v.counters[C_ERR],
                                    (unsigned long long)ERRF_DELTA);
@@ -1631,7 +1685,7 @@ struct GreedyRun {
 #endif
             hipLaunchKernelGGL(eval_rows_delta_kernel, dim3((unsigned)dblocks), dim3(DELTA_THREADS), DELTA_LDS_TOTAL, se,
                                (const uint4 *)sv.u_rows, (const unsigned long long *)&sv.tops[T_U], (long long)sv.cap_rows, &env->v.counters[C_ROWS_EVAL],
-                               (const float4 *)env->d_wt[slot], w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden,
+                               (const float4 *)env->net.d_wt[slot], w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden,
                                env->v.values, (const uint2 *)sv.u_info, sv.best, &env->v.counters[C_KSTEPS],
                                fused ? sv_next.tops : (unsigned long long *)nullptr, (int)T_COUNT, &env->v.counters[C_ERR],
                                (unsigned long long)ERRF_DELTA, sv.b_base > 0 ? (const unsigned long long *)&sv.tops[T_UB] : (const unsigned long long *)nullptr,
@@ -1660,7 +1714,7 @@ struct GreedyRun {
 #endif
                 if (root_ready)
                     hipLaunchKernelGGL(boundary_kernel<true>, grid1(n, BROOT_GPW), dim3(LANE_NT), BROOT_LDS_BYTES, s, ev, sv, sv_next, xv, flags, epsilon,
-                                       (const uint4 *)(ROOT_F16X2 ? env->d_wr2[slot] : env->d_wl3[slot]), (const uint2 *)(ROOT_F16X2 ? env->d_lut16 : env->d_lut), b1);
+                                       env->net.root_w(slot), env->net.root_lut(), b1);
                 else
                     hipLaunchKernelGGL(boundary_kernel<false>, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, ev, sv, sv_next, xv, flags, epsilon,
                                        (const uint4 *)nullptr, (const uint2 *)nullptr, (const float *)nullptr);
@@ -1671,6 +1725,7 @@ struct GreedyRun {
         }
         env->sv.tops = sv.tops;                                // the set whose T_U describes the last evaluated rows
         env->sv.b_base = sv.b_base;
+        first_of_run = false;
         if (fused) { parity ^= 1; sv = sv_next; }
         else if (more) {                                       // dense value-net modes: plain per-step sequence
             HIPCHK(hipMemsetAsync(sv.tops, 0, T_COUNT * 8, s));
@@ -1681,6 +1736,24 @@ struct GreedyRun {
         return BGAMD_OK;
     }
 };
+
+// One scoring pass over the virtual lanes 0 .. n_virtual, a scratch env's worth at a time (env->scratch: ready, see scratch_env).
+// seed(lanes, v0) launches the kernel that makes the virtual lanes from v0 on the lanes of that env; they are scored as a greedy step
+// scores its roots, and srch_collect_kernel writes out[v] of every virtual lane v that has a score: out is [n_virtual / 21][21].
+template <class Seed>
+int score_virtual_lanes(bgamd_env *env, int slot, long long n_virtual, const Seed &seed, float *out, hipStream_t s)
+{
+    bgamd_env *sc = env->scratch;
+    for (long long v0 = 0; v0 < n_virtual; v0 += sc->v.n) {
+        seed(sc->v, v0);
+        GreedyRun sr;
+        if (int rc = sr.score(sc, slot ? BGAMD_WEIGHTS_SLOT1 : 0, s)) return rc;
+        hipLaunchKernelGGL(srch_collect_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, (const unsigned long long *)sc->sv.best,
+                           (const float *)sc->sv.root_hidden, env->net.w2(slot), env->net.b2(slot), v0, out);
+    }
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
 
 }  // namespace
 
@@ -1699,7 +1772,7 @@ int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision
     rc = run.begin(s);
     if (rc) return rc;
     for (int64_t step = 0; step < n_steps; ++step) {
-        rc = run.step(ss, step + 1 < n_steps, step == 0);
+        rc = run.step(ss, step + 1 < n_steps);
         if (rc) return rc;
     }
     HIPCHK(hipGetLastError());
@@ -1711,82 +1784,77 @@ int bgamd_env_step_greedy(bgamd_env *env, int flags, float epsilon, int precisio
     return bgamd_env_run_greedy(env, flags, epsilon, precision, 1, stream);
 }
 
-// ---- 2-ply expectimax (bg_search.h) ---------------------------------------------------------------------------------------
-// Virtual lanes per pass of stage C: the scratch env has at most this many lanes (a 131 072-lane env: ~3.4 GB).  Every virtual
+// ---- what the 2-ply search, the pre-roll evaluation and the rollouts share --------------------------------------------------------
+// Virtual lanes per scoring pass: the search's scratch env has at most this many lanes (a 131 072-lane env: ~3.4 GB).  Every virtual
 // lane is scored on its own, so no result depends on it.
 constexpr long long SEARCH_CHUNK = 131072;
+// the lanes env->scratch needs for n_virtual virtual lanes: rounded up to 256, at most SEARCH_CHUNK
+static long long search_lanes(long long n_virtual) { return n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK; }
 
-// a scratch env (borrows_weights) points at its parent's weight tables as they are now
-static void scratch_borrow(const bgamd_env *env, bgamd_env *sc)
+// *which (env->scratch or env->rscratch) ready to use: an env on env's device with want_lanes lanes -- exactly that many (exact), else
+// at least that many -- created, or after a wait for s re-created, when the one at hand does not do.  Leaves env's device current and
+// the scratch env's weight tables those of env as they are now: a reload since the last call is seen.
+static int scratch_env(bgamd_env *env, bgamd_env **which, long long want_lanes, bool exact, uint64_t lane_stride, hipStream_t s)
 {
-    for (int k = 0; k < 2; ++k) {
-        sc->d_w[k] = env->d_w[k]; sc->d_wl[k] = env->d_wl[k]; sc->d_wt[k] = env->d_wt[k]; sc->d_wm[k] = env->d_wm[k];
-        sc->wm_ok[k] = env->wm_ok[k]; sc->d_wl3[k] = env->d_wl3[k]; sc->d_wr2[k] = env->d_wr2[k]; sc->d_wl16[k] = env->d_wl16[k];
-        sc->d_wlx2[k] = env->d_wlx2[k]; sc->d_wd16[k] = env->d_wd16[k]; sc->has_weights[k] = env->has_weights[k];
-    }
-    sc->d_lut = env->d_lut; sc->d_lut16 = env->d_lut16;
-}
-
-// the search's scratch env, with at least min(SEARCH_CHUNK, n_virtual rounded up to 256) lanes (re-created when it has fewer)
-static int search_scratch(bgamd_env *env, long long n_virtual, hipStream_t s)
-{
-    const long long want = n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK;
-    if (env->scratch && env->scratch->v.n < want) {
+    bgamd_env *&sc = *which;
+    if (sc && (exact ? sc->v.n != want_lanes : sc->v.n < want_lanes)) {
         HIPCHK(hipStreamSynchronize(s));
-        bgamd_env_destroy(env->scratch);
-        env->scratch = nullptr;
+        bgamd_env_destroy(sc);
+        sc = nullptr;
     }
-    if (!env->scratch) {
-        bgamd_env *sc = nullptr;
-        const int rc = env_create(&sc, want, env->device, 0, 0, 0, 0, true);
+    if (!sc) {
+        const int rc = env_create(&sc, want_lanes, env->device, 0, 0, lane_stride, 0, true);
         if (rc) return rc;
         HIPCHK(hipDeviceSynchronize());                // (its reset ran on the null stream)
-        env->scratch = sc;
     }
     HIPCHK(hipSetDevice(env->device));
+    sc->net = env->net;
     return BGAMD_OK;
 }
 
-static int search_grow(bgamd_env *env, long long need)
+// Caller-provided positions [n][28] (+ turn) as rows; a bad state is refused before anything is done with them (synchronises).
+// PRECONDITION: the caller has cleared env->a_ctr[A_INTAKE] on s.  The clear is not done here because the rollout clears its own
+// counters with the same fill (see bgamd_env::a_ctr) and then one more buffer before the pack: doing it here would add a launch to
+// the rollout or reorder its launches.  The bad-state word is read into a pageable local; the synchronise below covers that copy.
+static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int32_t *d_turn, long long n, uint4 *rows, hipStream_t s)
 {
-    if (need <= env->c_cap) return BGAMD_OK;
-    void *old[] = {env->c_rows, env->c_key, env->c_v1, env->c_v2, env->c_rval};
-    for (void *p : old) if (p) HIPCHK(hipFree(p));
-    env->c_rows = nullptr; env->c_key = nullptr; env->c_v1 = env->c_v2 = env->c_rval = nullptr; env->c_cap = 0;
-    const long long cap = need < 1024 ? 1024 : need;
-    HIPCHK(hipMalloc(&env->c_rows, (size_t)cap * 32));
-    HIPCHK(hipMalloc(&env->c_key, (size_t)cap * 4));
-    HIPCHK(hipMalloc(&env->c_v1, (size_t)cap * 4));
-    HIPCHK(hipMalloc(&env->c_v2, (size_t)cap * 4));
-    HIPCHK(hipMalloc(&env->c_rval, (size_t)cap * SRCH_ROLLS * 4));
-    env->c_cap = cap;
-    return BGAMD_OK;
+    unsigned long long h = 0;
+    hipLaunchKernelGGL(pack_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_turn, n, rows, &env->a_ctr[A_INTAKE]);
+    HIPCHK(hipMemcpyAsync(&h, &env->a_ctr[A_INTAKE], 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return (h & ERRF_STATE) ? BGAMD_E_STATE : BGAMD_OK;
 }
 
+// ---- 2-ply expectimax (bg_search.h) ---------------------------------------------------------------------------------------
 int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
 {
     if (!env || top_k < 0) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
     if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
+    if (!env->net.has_weights[(flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0]) return BGAMD_E_NOWEIGHTS;
     hipStream_t s = (hipStream_t)stream;
     const long long n = env->v.n;
-    GreedyRun run;
-    int rc = run.init(env, flags, 0.0f, BGAMD_F32);
-    if (rc) return rc;
-    if (!env->s_cnt) {
-        uint32_t **per_game[] = {&env->s_cnt, &env->s_off, &env->s_fill, &env->s_kept, &env->s_koff};
+    SearchState &se = env->srch;
+    int rc;
+    if (!se.cnt) {
+        uint32_t **per_game[] = {&se.cnt, &se.off, &se.fill, &se.kept, &se.koff};
         for (uint32_t **p : per_game) HIPCHK(hipMalloc(p, (size_t)(n + 1) * 4));
-        HIPCHK(hipMalloc(&env->s_max, 8));
-        HIPCHK(hipMalloc(&env->s_grp, (size_t)env->sv.cap_rows * 4));
-        HIPCHK(hipMalloc(&env->s_rank, (size_t)env->sv.cap_rows * 4));
+        HIPCHK(hipMalloc(&se.max, 8));
+        HIPCHK(hipMalloc(&se.grp, (size_t)env->sv.cap_rows * 4));
+        HIPCHK(hipMalloc(&se.rank, (size_t)env->sv.cap_rows * 4));
     }
+    auto grow_candidates = [&](long long need) {       // (at least 1 024 rows once there is one)
+        return grow_buffers(need > 0 && need < 1024 ? 1024 : need, se.c_cap,
+                            {{(void **)&se.c_rows, 32}, {(void **)&se.c_key, 4}, {(void **)&se.c_v1, 4}, {(void **)&se.c_v2, 4},
+                             {(void **)&se.c_rval, 4 * SRCH_ROLLS}});
+    };
     long long n_cand = top_k > 0 ? n * (long long)top_k : 0;         // bound on the kept candidates (top_k = 0: read back below)
-    if (top_k > 0 && (rc = search_grow(env, n_cand))) return rc;
-    env->search_k = -1;
+    if (top_k > 0 && (rc = grow_candidates(n_cand))) return rc;
+    se.k = -1;
 
     // stage A: the greedy step's roots, expansion and incremental value net, no apply
-    const StepStreams ss{s, s, env->n_cu};
-    if ((rc = run.begin(s)) || (rc = run.step(ss, false, true, true))) return rc;
+    GreedyRun run;
+    if ((rc = run.score(env, flags, s))) return rc;
 
     // stage B: group by game, select, list the kept candidates
     const unsigned long long *tops = env->sv.tops;
@@ -1794,119 +1862,87 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
     const uint2 *info = env->sv.u_info;
     const uint4 *rows = env->sv.u_rows;
     const dim3 rgrid((unsigned)(env->n_cu * 8));
-    HIPCHK(hipMemsetAsync(env->s_cnt, 0, (size_t)n * 4, s));
-    HIPCHK(hipMemsetAsync(env->s_fill, 0, (size_t)n * 4, s));
-    hipLaunchKernelGGL(srch_count_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, env->s_cnt);
-    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)env->s_cnt, env->s_off, n, (uint32_t *)nullptr);
-    hipLaunchKernelGGL(srch_scatter_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, (const uint32_t *)env->s_off, env->s_fill,
-                       env->s_grp);
+    HIPCHK(hipMemsetAsync(se.cnt, 0, (size_t)n * 4, s));
+    HIPCHK(hipMemsetAsync(se.fill, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(srch_count_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, se.cnt);
+    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.cnt, se.off, n, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(srch_scatter_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, (const uint32_t *)se.off, se.fill, se.grp);
     const uint32_t k_lim = top_k > 0 ? (uint32_t)top_k : 0xFFFFFFFFu;
-    hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)env->s_cnt, (const uint32_t *)env->s_off,
-                       (const uint32_t *)env->s_grp, rows, info, (const float *)env->v.values, k_lim, env->s_rank, env->s_kept);
-    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)env->s_kept, env->s_koff, n, env->s_max);
+    hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                       (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept);
+    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.kept, se.koff, n, se.max);
     int K = top_k;
     if (top_k == 0) {                                  // every distinct afterstate: the list's length is read back (the one synchronisation)
         uint32_t h[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(&h[0], env->s_koff + n, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&h[1], env->s_max, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h[0], se.koff + n, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h[1], se.max, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         n_cand = h[0]; K = (int)h[1];
-        if ((rc = search_grow(env, n_cand))) return rc;
+        if ((rc = grow_candidates(n_cand))) return rc;
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(srch_emit_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint32_t *)env->s_cnt, (const uint32_t *)env->s_off,
-                       (const uint32_t *)env->s_grp, rows, info, (const float *)env->v.values, (const int32_t *)env->s_rank,
-                       (const uint32_t *)env->s_koff, env->c_rows, env->c_key, env->c_v1);
+    hipLaunchKernelGGL(srch_emit_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                       (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, (const int32_t *)se.rank,
+                       (const uint32_t *)se.koff, se.c_rows, se.c_key, se.c_v1);
 
-    // stage C: one virtual lane per (candidate, opponent roll), SEARCH_CHUNK at a time through the scratch env
-    const int slot = run.slot;
+    // stage C: one virtual lane per (candidate, opponent roll), scored on the scratch env
     const long long n_virtual = n_cand * SRCH_ROLLS;
     if (n_virtual > 0) {
-        if ((rc = search_scratch(env, n_virtual, s))) return rc;
-        bgamd_env *sc = env->scratch;
-        scratch_borrow(env, sc);                       // the tables of this env as they are now: a reload is seen
-        const float *w2 = env->d_w[slot] + N_HID * N_IN + N_HID, *b2 = w2 + N_HID;
-        const StepStreams sss{s, s, sc->n_cu};
-        for (long long v0 = 0; v0 < n_virtual; v0 += sc->v.n) {
-            hipLaunchKernelGGL(srch_fanout_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, v0,
-                               (const uint32_t *)(env->s_koff + n), (const uint4 *)env->c_rows, (const uint32_t *)env->c_key);
-            GreedyRun sr;
-            if ((rc = sr.init(sc, flags & BGAMD_WEIGHTS_SLOT1, 0.0f, BGAMD_F32)) || (rc = sr.begin(s)) ||
-                (rc = sr.step(sss, false, true, true)))
-                return rc;
-            hipLaunchKernelGGL(srch_collect_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, (const unsigned long long *)sc->sv.best,
-                               (const float *)sc->sv.root_hidden, w2, b2, v0, env->c_rval);
-        }
+        if ((rc = scratch_env(env, &env->scratch, search_lanes(n_virtual), false, 0, s))) return rc;
+        const auto fanout = [&](const EnvView &lanes, long long v0) {
+            hipLaunchKernelGGL(srch_fanout_kernel, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.koff + n),
+                               (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
+        };
+        if ((rc = score_virtual_lanes(env, run.slot, n_virtual, fanout, se.c_rval, s))) return rc;
     }
 
     // stage D: V2, choice, and the greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice)
-    hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)env->s_kept,
-                       (const uint32_t *)env->s_koff, (const uint4 *)env->c_rows, (const uint32_t *)env->c_key, (const float *)env->c_v1,
-                       (const float *)env->c_rval, env->c_v2, env->sv.best, &env->v.counters[C_ERR],
+    hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                       (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
+                       (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR],
                        env->scratch ? &env->scratch->v.counters[C_ERR] : (unsigned long long *)nullptr);
     const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
     hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
     HIPCHK(hipGetLastError());
-    env->search_k = K;
+    se.k = K;
     return BGAMD_OK;
 }
 
 int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream)
 {
     ENV_GUARD(env);
-    if (env->search_k < 0) return BGAMD_E_INVALID;
+    const SearchState &se = env->srch;
+    if (se.k < 0) return BGAMD_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const long long n = env->v.n;
-    const int K = env->search_k;
-    if (d_kept) hipLaunchKernelGGL(srch_kept_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)env->s_kept, d_kept);
+    const long long n = env->v.n, K = se.k;
+    if (d_kept) hipLaunchKernelGGL(srch_kept_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept, d_kept);
     if (K > 0 && (d_states28 || d_v1 || d_v2))
-        hipLaunchKernelGGL(srch_read_kernel, grid1(n * K, SRCH_NT), dim3(SRCH_NT), 0, s, n, K, (const uint32_t *)env->s_kept,
-                           (const uint32_t *)env->s_koff, (const uint4 *)env->c_rows, (const float *)env->c_v1, (const float *)env->c_v2,
+        hipLaunchKernelGGL(srch_read_kernel, grid1(n * K, SRCH_NT), dim3(SRCH_NT), 0, s, n, (int)K, (const uint32_t *)se.kept,
+                           (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const float *)se.c_v1, (const float *)se.c_v2,
                            d_states28, d_v1, d_v2);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
 
-// ---- Monte Carlo rollouts (bg_rollout.h) -----------------------------------------------------------------------------------
-// Default lanes of the scratch env that plays the trials (a 65 536-lane env: ~1.7 GB); fewer when the call has fewer trials.
-constexpr long long ROLLOUT_LANES = 65536;
-// Turns per run between two refill points (M > 0: the largest divisor of the turns a trial has left at its start not above it).  A trial
-// that ends inside a run leaves its lane idle for the rest of the run: R / 2 turns per trial on average, against ~83 per game.
-constexpr int ROLLOUT_RUN = 8;
-
-static int ro_grow(long long need, long long &cap, std::initializer_list<std::pair<void **, size_t>> bufs)
-{
-    if (need <= cap) return BGAMD_OK;
-    for (auto &b : bufs) { if (*b.first) HIPCHK(hipFree(*b.first)); *b.first = nullptr; }
-    cap = 0;
-    for (auto &b : bufs) HIPCHK(hipMalloc(b.first, (size_t)need * b.second));
-    cap = need;
-    return BGAMD_OK;
-}
-
 // ---- pre-roll evaluation (bg_vr.h) ---------------------------------------------------------------------------------------
 // f of n positions x 21 rolls: the positions are rows[n] (src NULL) or the lanes of the env src (n = its lane count); every (position,
-// roll) is a virtual lane of the search's scratch env (search_scratch: ready, weights borrowed), scored as the search's stage C scores
-// its roots.  Writes f[q][r] of every position that is neither over nor a finished lane.
+// roll) is a virtual lane of the search's scratch env.  Writes f[q][r] of every position that is neither over nor a finished lane.
 static int preroll_pass(bgamd_env *env, int slot, long long n, const uint4 *rows, const EnvView *src, float *f, hipStream_t s)
 {
-    bgamd_env *sc = env->scratch;
-    const float *w2 = env->d_w[slot] + N_HID * N_IN + N_HID, *b2 = w2 + N_HID;
-    const StepStreams sss{s, s, sc->n_cu};
-    const long long n_virtual = n * SRCH_ROLLS;
-    for (long long v0 = 0; v0 < n_virtual; v0 += sc->v.n) {
+    const auto fanout = [&](const EnvView &lanes, long long v0) {
         if (src)
-            hipLaunchKernelGGL(pre_fanout_kernel<true>, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, v0, n, (const uint4 *)nullptr, *src);
+            hipLaunchKernelGGL(pre_fanout_kernel<true>, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, n, (const uint4 *)nullptr, *src);
         else
-            hipLaunchKernelGGL(pre_fanout_kernel<false>, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, v0, n, rows, sc->v);
-        GreedyRun sr;
-        int rc;
-        if ((rc = sr.init(sc, slot ? BGAMD_WEIGHTS_SLOT1 : 0, 0.0f, BGAMD_F32)) || (rc = sr.begin(s)) || (rc = sr.step(sss, false, true, true)))
-            return rc;
-        hipLaunchKernelGGL(srch_collect_kernel, grid1(sc->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, sc->v, (const unsigned long long *)sc->sv.best,
-                           (const float *)sc->sv.root_hidden, w2, b2, v0, f);
-    }
-    HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(pre_fanout_kernel<false>, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, n, rows, lanes);
+    };
+    return score_virtual_lanes(env, slot, n * SRCH_ROLLS, fanout, f, s);
+}
+
+// the search's scratch env for n positions x 21 rolls, its error bits cleared: what preroll_pass scores on, preroll_errors reads
+static int preroll_begin(bgamd_env *env, long long n, hipStream_t s)
+{
+    if (int rc = scratch_env(env, &env->scratch, search_lanes(n * SRCH_ROLLS), false, 0, s)) return rc;
+    HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
     return BGAMD_OK;
 }
 
@@ -1926,93 +1962,75 @@ int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_state
     if (!env || !d_states28 || n < 1 || n >= (1ll << 31) / SRCH_ROLLS || (flags & ~BGAMD_WEIGHTS_SLOT1)) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
     const int slot = (flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
-    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
     hipStream_t s = (hipStream_t)stream;
+    PrerollState &pre = env->pre;
     int rc;
-    if ((rc = ro_grow(n, env->p_cap, {{(void **)&env->p_rows, 32}, {(void **)&env->p_f, 4 * SRCH_ROLLS}}))) return rc;
-    if (!env->p_ctr) HIPCHK(hipMalloc(&env->p_ctr, 8));
+    if ((rc = grow_buffers(n, pre.cap, {{(void **)&pre.rows, 32}, {(void **)&pre.f, 4 * SRCH_ROLLS}}))) return rc;
 
-    // the positions as rows; a bad state is refused before anything is scored
-    unsigned long long h = 0;
-    HIPCHK(hipMemsetAsync(env->p_ctr, 0, 8, s));
-    hipLaunchKernelGGL(pack_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_turn, (long long)n, env->p_rows, env->p_ctr);
-    HIPCHK(hipMemcpyAsync(&h, env->p_ctr, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h & ERRF_STATE) return BGAMD_E_STATE;
+    HIPCHK(hipMemsetAsync(&env->a_ctr[A_INTAKE], 0, 8, s));
+    if ((rc = intake_positions(env, d_states28, d_turn, n, pre.rows, s))) return rc;
 
-    if ((rc = search_scratch(env, n * SRCH_ROLLS, s))) return rc;
-    scratch_borrow(env, env->scratch);
-    HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
-    if ((rc = preroll_pass(env, slot, n, env->p_rows, nullptr, env->p_f, s))) return rc;
-    hipLaunchKernelGGL(pre_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)n, (const uint4 *)env->p_rows, env->p_f,
+    if ((rc = preroll_begin(env, n, s)) || (rc = preroll_pass(env, slot, n, pre.rows, nullptr, pre.f, s))) return rc;
+    hipLaunchKernelGGL(pre_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)n, (const uint4 *)pre.rows, pre.f,
                        d_roll_values, d_mean);
     HIPCHK(hipGetLastError());
     return preroll_errors(env, s);
 }
+
+// ---- Monte Carlo rollouts (bg_rollout.h) -----------------------------------------------------------------------------------
+// Default lanes of the scratch env that plays the trials (a 65 536-lane env: ~1.7 GB); fewer when the call has fewer trials.
+constexpr long long ROLLOUT_LANES = 65536;
+// Turns per run between two refill points (M > 0: the largest divisor of the turns a trial has left at its start not above it).  A trial
+// that ends inside a run leaves its lane idle for the rest of the run: R / 2 turns per trial on average, against ~83 per game.
+constexpr int ROLLOUT_RUN = 8;
 
 int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n_positions,
                       int64_t position_offset, int64_t trials, int64_t max_plies, uint64_t seed, int64_t lanes,
                       double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
                       float *d_trial_value, int32_t *d_trial_turns, void *stream)
 {
-    if (env) env->r_vr_P = 0;                          // (bgamd_env_rollout_vr_read: only after a call that had the flag)
+    if (env) env->ro.vr_P = 0;                         // (bgamd_env_rollout_vr_read: only after a call that had the flag)
     if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
     if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1 | BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
     if (n_positions >= (1ll << 31) || trials >= (1ll << 31) || n_positions * trials >= (1ll << 31) || lanes > (1ll << 30))
         return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
     const int slot = (flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
-    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
     hipStream_t s = (hipStream_t)stream;
     const long long P = n_positions, T = trials, N = P * T, M = max_plies;
     const bool rotate = (flags & BGAMD_ROLLOUT_ROTATE) != 0, vr = (flags & BGAMD_ROLLOUT_VR) != 0;
     const long long F = rotate ? (T < 36 ? T : 36) : 0, n_fan = P * F;
     const long long L = lanes > 0 ? lanes : (N < ROLLOUT_LANES ? ((N + 255) / 256) * 256 : ROLLOUT_LANES);
+    RolloutState &ro = env->ro;
     int rc;
 
-    // the scratch env and the buffers of this call
-    if (env->rscratch && env->rscratch->v.n != L) {
-        HIPCHK(hipStreamSynchronize(s));
-        bgamd_env_destroy(env->rscratch);
-        env->rscratch = nullptr;
-    }
-    if (!env->rscratch) {
-        bgamd_env *sc = nullptr;
-        if ((rc = env_create(&sc, L, env->device, 0, 0, 1, 0, true))) return rc;
-        HIPCHK(hipDeviceSynchronize());                // (its reset ran on the null stream)
-        env->rscratch = sc;
-    }
-    HIPCHK(hipSetDevice(env->device));
+    // the scratch env (exactly L lanes) and the buffers of this call
+    if ((rc = scratch_env(env, &env->rscratch, L, true, 1, s))) return rc;
     bgamd_env *sc = env->rscratch;
-    scratch_borrow(env, sc);
-    if ((rc = ro_grow(P, env->r_cap_pos, {{(void **)&env->r_pos, 32}})) ||
-        (rc = ro_grow(n_fan, env->r_cap_fan, {{(void **)&env->r_fan, 32}, {(void **)&env->r_fval, 4}})) ||
-        (rc = ro_grow(N, env->r_cap_trials, {{(void **)&env->r_tval, 4}, {(void **)&env->r_tturns, 4}})) ||
-        (rc = ro_grow(L, env->r_cap_lanes, {{(void **)&env->r_lane, 4}, {(void **)&env->r_trows, 32}, {(void **)&env->r_tids, 4},
-                                            {(void **)&env->r_tv, 4}})))
+    if ((rc = grow_buffers(P, ro.cap_pos, {{(void **)&ro.pos, 32}})) ||
+        (rc = grow_buffers(n_fan, ro.cap_fan, {{(void **)&ro.fan, 32}, {(void **)&ro.fval, 4}})) ||
+        (rc = grow_buffers(N, ro.cap_trials, {{(void **)&ro.tval, 4}, {(void **)&ro.tturns, 4}})) ||
+        (rc = grow_buffers(L, ro.cap_lanes, {{(void **)&ro.lane, 4}, {(void **)&ro.trows, 32}, {(void **)&ro.tids, 4}, {(void **)&ro.tv, 4}})))
         return rc;
-    if (vr && ((rc = ro_grow(N, env->r_cap_vtrials, {{(void **)&env->r_tluck, 8}})) ||
-               (rc = ro_grow(L, env->r_cap_vlanes, {{(void **)&env->r_vf, 4 * SRCH_ROLLS}})) ||
-               (rc = ro_grow(P, env->r_cap_vpos, {{(void **)&env->r_f0, 4 * SRCH_ROLLS}, {(void **)&env->r_m0, 8}}))))
+    if (vr && ((rc = grow_buffers(N, ro.cap_vtrials, {{(void **)&ro.tluck, 8}})) ||
+               (rc = grow_buffers(L, ro.cap_vlanes, {{(void **)&ro.vf, 4 * SRCH_ROLLS}})) ||
+               (rc = grow_buffers(P, ro.cap_vpos, {{(void **)&ro.f0, 4 * SRCH_ROLLS}, {(void **)&ro.m0, 8}}))))
         return rc;
-    if (!env->r_ctr) HIPCHK(hipMalloc(&env->r_ctr, RO_CTRS * 8));
-    if (!env->r_host) HIPCHK(hipHostMalloc(&env->r_host, 8 * 8));
-    unsigned long long *h = env->r_host;
+    if ((rc = ro.read_back_ready())) return rc;
+    unsigned long long *h = ro.host, *ctr = env->a_ctr;
 
     // the positions as rows; a bad state is refused before anything is played
-    HIPCHK(hipMemsetAsync(env->r_ctr, 0, RO_CTRS * 8, s));
+    HIPCHK(hipMemsetAsync(env->a_ctr, 0, A_WORDS * 8, s));
     HIPCHK(hipMemsetAsync(sc->v.counters, 0, C_COUNT * 8, s));
-    hipLaunchKernelGGL(pack_rows_kernel, grid1(P, 128), dim3(128), 0, s, d_states28, d_turn, (long long)P, env->r_pos, &env->r_ctr[RO_ERR]);
-    HIPCHK(hipMemcpyAsync(h, &env->r_ctr[RO_ERR], 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h[0] & ERRF_STATE) return BGAMD_E_STATE;
+    if ((rc = intake_positions(env, d_states28, d_turn, P, ro.pos, s))) return rc;
 
     // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1
     sc->v.seed = seed;
     sc->v.lane_stride = 1;
     sc->v.lane_offset = (unsigned long long)position_offset * (unsigned long long)T - (unsigned long long)L;
-    const RoView r{N, T, M, rotate ? 1 : 0, F, env->r_pos, env->r_fan, env->r_fval, env->r_lane, env->r_tval, env->r_tturns, env->r_trows,
-                   env->r_tids, env->r_ctr};
+    const RoView r{N, T, M, rotate ? 1 : 0, F, ro.pos, ro.fan, ro.fval, ro.lane, ro.tval, ro.tturns, ro.trows, ro.tids, ctr};
     const int run_flags = flags & BGAMD_WEIGHTS_SLOT1;
     const StepStreams ss{s, sc->overlap ? sc->side : s, sc->n_cu};
     long long steps = 0;
@@ -2021,36 +2039,30 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     if (rotate) {
         for (long long v0 = 0; v0 < n_fan; v0 += L) {
             hipLaunchKernelGGL(ro_fan_seed_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, r);
-            GreedyRun fr;
-            if ((rc = fr.init(sc, run_flags, 0.0f, BGAMD_F32)) || (rc = fr.begin(s)) || (rc = fr.step(ss, false))) return rc;
-            hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, env->r_fan);
+            if ((rc = bgamd_env_step_greedy(sc, run_flags, 0.0f, BGAMD_F32, s))) return rc;
+            hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, ro.fan);
             ++steps;
         }
-        if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, nullptr, n_fan, env->r_fan, env->r_fval, nullptr, nullptr, s))) return rc;
+        if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, nullptr, n_fan, ro.fan, ro.fval, nullptr, nullptr, s))) return rc;
     }
 
     // luck adjustment: the pre-roll evaluation on the search's scratch env -- of the P positions once (rotation: turn 0's luck), then
     // of the trial lanes before every turn (vr_turn); every trial's luck total starts at 0 or at its turn-0 luck
     if (vr) {
-        const long long pv = (rotate ? P : 0) > L ? P : L;
-        if ((rc = search_scratch(env, pv * SRCH_ROLLS, s))) return rc;
-        scratch_borrow(env, env->scratch);
-        HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
+        if ((rc = preroll_begin(env, (rotate ? P : 0) > L ? P : L, s))) return rc;
         if (rotate) {
-            if ((rc = preroll_pass(env, slot, P, env->r_pos, nullptr, env->r_f0, s))) return rc;
-            hipLaunchKernelGGL(pre_reduce_kernel, grid1(P, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)P, (const uint4 *)env->r_pos, env->r_f0,
-                               (float *)nullptr, env->r_m0);
+            if ((rc = preroll_pass(env, slot, P, ro.pos, nullptr, ro.f0, s))) return rc;
+            hipLaunchKernelGGL(pre_reduce_kernel, grid1(P, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)P, (const uint4 *)ro.pos, ro.f0,
+                               (float *)nullptr, ro.m0);
         }
-        hipLaunchKernelGGL(ro_vr_init_kernel, dim3((unsigned)(sc->n_cu * 4)), dim3(RO_NT), 0, s, r, (const float *)env->r_f0,
-                           (const double *)env->r_m0, env->r_tluck);
+        hipLaunchKernelGGL(ro_vr_init_kernel, dim3((unsigned)(sc->n_cu * 4)), dim3(RO_NT), 0, s, r, (const float *)ro.f0,
+                           (const double *)ro.m0, ro.tluck);
         HIPCHK(hipGetLastError());
     }
     // (the roots of the turn at hand are in place: the board, side to move and dice of every live trial lane)
     auto vr_turn = [&]() -> int {
-        const int e = preroll_pass(env, slot, L, nullptr, &sc->v, env->r_vf, s);
-        if (e) return e;
-        hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)env->r_lane, (const float *)env->r_vf,
-                           env->r_tluck);
+        if (const int e = preroll_pass(env, slot, L, nullptr, &sc->v, ro.vf, s)) return e;
+        hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)ro.lane, (const float *)ro.vf, ro.tluck);
         return BGAMD_OK;
     };
 
@@ -2065,32 +2077,34 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     auto refill = [&]() -> int {
         hipLaunchKernelGGL(ro_refill_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, r);
         if (M > 0) {                                   // truncated trials: the dense fp32 evaluator of bgamd_evaluate_slot
-            const int e = launch_eval(sc, slot, BGAMD_F32, &env->r_ctr[RO_NTRUNC], L, env->r_trows, env->r_tv, nullptr, nullptr, s);
-            if (e) return e;
-            hipLaunchKernelGGL(ro_trunc_scatter_kernel, dim3((unsigned)sc->n_cu), dim3(RO_NT), 0, s, r, (const float *)env->r_tv);
-            HIPCHK(hipMemsetAsync(&env->r_ctr[RO_NTRUNC], 0, 8, s));
+            if (const int e = launch_eval(sc, slot, BGAMD_F32, &ctr[RO_NTRUNC], L, ro.trows, ro.tv, nullptr, nullptr, s)) return e;
+            hipLaunchKernelGGL(ro_trunc_scatter_kernel, dim3((unsigned)sc->n_cu), dim3(RO_NT), 0, s, r, (const float *)ro.tv);
+            HIPCHK(hipMemsetAsync(&ctr[RO_NTRUNC], 0, 8, s));
         }
         HIPCHK(hipGetLastError());
         return BGAMD_OK;
     };
-    HIPCHK(hipMemsetAsync(env->r_lane, 0xFF, (size_t)L * 4, s));
+    HIPCHK(hipMemsetAsync(ro.lane, 0xFF, (size_t)L * 4, s));
     if ((rc = refill())) return rc;
 
-    // the loop: G runs of R turns with a refill after each, then an asynchronous read of (done, errors) into pinned memory; the host
-    // waits for the read before the last one, so the device always has a group queued
-    hipEvent_t evr[2] = {nullptr, nullptr};
-    HIPCHK(hipEventCreateWithFlags(&evr[0], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&evr[1], hipEventDisableTiming));
+    // (trials done, truncated now, the rollout's error bits, the trial env's error bits) -> dst[0 .. 3], asynchronously
+    auto read_back = [&](unsigned long long *dst) -> int {
+        HIPCHK(hipMemcpyAsync(dst, &ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(dst + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
+        return BGAMD_OK;
+    };
+    // the loop: G runs of R turns with a refill after each, then a read-back into pinned memory; the host waits for the read before
+    // the last one, so the device always has a group queued
     auto loop = [&]() -> int {
         unsigned long long last_done = 0;
         long long stalled = 0;
         for (int k = 0;; ++k) {
             const int b = k & 1;
-            HIPCHK(hipMemcpyAsync(h + 4 * b, &env->r_ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(h + 4 * b + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipEventRecord(evr[b], s));
+            int e;
+            if ((e = read_back(h + 4 * b))) return e;
+            HIPCHK(hipEventRecord(ro.ev[b], s));
             if (k > 0) {
-                HIPCHK(hipEventSynchronize(evr[b ^ 1]));
+                HIPCHK(hipEventSynchronize(ro.ev[b ^ 1]));
                 const unsigned long long *hp = h + 4 * (b ^ 1);
                 if (hp[0] >= (unsigned long long)N || hp[2] || hp[3]) return BGAMD_OK;
                 stalled = hp[0] == last_done ? stalled + (long long)G * R : 0;
@@ -2099,10 +2113,9 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
             }
             for (int gi = 0; gi < G; ++gi) {
                 GreedyRun run;
-                int e;
                 if ((e = run.init(sc, BGAMD_ROLL | run_flags, 0.0f, BGAMD_F32)) || (e = run.begin(s))) return e;
                 for (int t = 0; t < R; ++t)
-                    if ((vr && (e = vr_turn())) || (e = run.step(ss, t + 1 < R, t == 0))) return e;
+                    if ((vr && (e = vr_turn())) || (e = run.step(ss, t + 1 < R))) return e;
                 steps += R;
                 if ((e = refill())) return e;
             }
@@ -2110,40 +2123,37 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     };
     rc = loop();
     hipStreamSynchronize(s);
-    hipEventDestroy(evr[0]);
-    hipEventDestroy(evr[1]);
     if (rc) return rc;
 
-    HIPCHK(hipMemcpyAsync(h, &env->r_ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
+    if ((rc = read_back(h))) return rc;
     HIPCHK(hipMemcpyAsync(h + 4, &sc->v.counters[C_STEPS], 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if ((rc = check_err_flags(sc, h[3]))) return rc;
     if (h[2] & (ERRF_RO_LONG | ERRF_RO_PLY) || h[0] != (unsigned long long)N) return BGAMD_E_INVALID;
     if (vr && (rc = preroll_errors(env, s))) return rc;
-    env->r_info[0] = L; env->r_info[1] = steps; env->r_info[2] = (int64_t)h[4]; env->r_info[3] = R;
+    ro.info[0] = L; ro.info[1] = steps; ro.info[2] = (int64_t)h[4]; ro.info[3] = R;
 
-    hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)P), dim3(64), 0, s, (long long)T, (const float *)env->r_tval,
-                       (const uint32_t *)env->r_tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
+    hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)P), dim3(64), 0, s, (long long)T, (const float *)ro.tval,
+                       (const uint32_t *)ro.tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    if (vr) { env->r_vr_P = P; env->r_vr_T = T; }
+    if (vr) { ro.vr_P = P; ro.vr_T = T; }
     return BGAMD_OK;
 }
 
 int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4])
 {
     if (!env || !h_out) return BGAMD_E_INVALID;
-    for (int k = 0; k < 4; ++k) h_out[k] = env->r_info[k];
+    for (int k = 0; k < 4; ++k) h_out[k] = env->ro.info[k];
     return BGAMD_OK;
 }
 
 int bgamd_env_rollout_vr_read(bgamd_env *env, double *d_vr_mean, double *d_vr_stderr, double *d_trial_luck, void *stream)
 {
     ENV_GUARD(env);
-    if (env->r_vr_P < 1) return BGAMD_E_INVALID;
-    hipLaunchKernelGGL(ro_vr_reduce_kernel, dim3((unsigned)env->r_vr_P), dim3(64), 0, (hipStream_t)stream, (long long)env->r_vr_T,
-                       (const float *)env->r_tval, (const double *)env->r_tluck, d_vr_mean, d_vr_stderr, d_trial_luck);
+    if (env->ro.vr_P < 1) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL(ro_vr_reduce_kernel, dim3((unsigned)env->ro.vr_P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.vr_T,
+                       (const float *)env->ro.tval, (const double *)env->ro.tluck, d_vr_mean, d_vr_stderr, d_trial_luck);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
@@ -2296,7 +2306,7 @@ int bgamd_evaluate_slot(bgamd_env *env, int slot, const int32_t *d_states28, con
 {
     if (!env || slot < 0 || slot > 1 || !d_states28 || !d_values || n < 0 || n > env->v.cap) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
-    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
     if (n == 0) return BGAMD_OK;
     hipStream_t s = (hipStream_t)stream;
     // the candidate arena doubles as scratch for caller-provided states
@@ -2313,11 +2323,11 @@ int bgamd_evaluate_incremental(bgamd_env *env, int slot, const int32_t *d_root_s
         n_roots <= 0 || n_roots > env->v.n || n < 0 || n > env->sv.cap_rows)
         return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
-    if (!env->has_weights[slot]) return BGAMD_E_NOWEIGHTS;
+    if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
     if (n == 0) return BGAMD_OK;
     hipStream_t s = (hipStream_t)stream;
     StagedView &sv = env->sv;
-    const float *b1 = env->d_w[slot] + N_HID * N_IN, *w2 = b1 + N_HID, *b2 = w2 + N_HID;
+    const float *w2 = env->net.w2(slot), *b2 = env->net.b2(slot);
     // the env's root / afterstate arenas double as scratch, as the candidate arena does for bgamd_evaluate; the rows are written
     // linearly from 0: a later unique_rows_read must not remap them through the arena counters of an earlier greedy step
     sv.b_base = 0;
@@ -2326,36 +2336,21 @@ int bgamd_evaluate_incremental(bgamd_env *env, int slot, const int32_t *d_root_s
     hipLaunchKernelGGL(pack_child_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_root_index, (long long)n,
                        (long long)n_roots, (const uint4 *)sv.root_rows, sv.u_rows, sv.u_info, &env->v.counters[C_ERR]);
     HIPCHK(hipMemsetAsync(sv.best, 0, (size_t)n_roots * 8, s));
-#ifdef BGAMD_EXPERIMENTAL
-    if (!env->root_resident) {
-        long long blocks = ((n_roots + 31) / 32 + ROOT3_THREADS / 64 - 1) / (ROOT3_THREADS / 64);
-        if (blocks > env->n_cu) blocks = env->n_cu;
-        hipLaunchKernelGGL(root_hidden_bf16x3_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOT3_THREADS), ROOT3_LDS_TOTAL, s,
-                           (const uint4 *)sv.root_rows, (long long)n_roots, (const uint4 *)env->d_wl3[slot], (const uint2 *)env->d_lut, b1,
-                           sv.root_hidden);
-    } else
-#endif
-    {
-        long long blocks = (n_roots + 31) / 32;
-        if (blocks > 2ll * env->n_cu) blocks = 2ll * env->n_cu;
-        hipLaunchKernelGGL(root_hidden_resident_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOTR_THREADS), ROOTR_LDS_BYTES, s,
-                           (const uint4 *)sv.root_rows, (long long)n_roots, (const uint4 *)(ROOT_F16X2 ? env->d_wr2[slot] : env->d_wl3[slot]), (const uint2 *)(ROOT_F16X2 ? env->d_lut16 : env->d_lut), b1,
-                           sv.root_hidden);
-    }
+    launch_root_pass(env, slot, (const uint4 *)sv.root_rows, (long long)n_roots, sv.root_hidden, false, s);
     long long dblocks = (n + DELTA_THREADS - 1) / DELTA_THREADS;
     dblocks = dblocks < 1 ? 1 : (dblocks > env->n_cu ? env->n_cu : dblocks);
     KTimer t(env, s, 1);
 #ifdef BGAMD_EXPERIMENTAL
-    if (env->mfma_delta && env->wm_ok[slot])
+    if (env->mfma_delta && env->net.wm_ok[slot])
         hipLaunchKernelGGL(eval_rows_mdelta_kernel, dim3((unsigned)dblocks), dim3(MD_THREADS), MD_LDS_TOTAL, s, (const uint4 *)sv.u_rows,
-                           (const unsigned long long *)nullptr, (long long)n, (unsigned long long *)nullptr, (const uint4 *)env->d_wm[slot],
+                           (const unsigned long long *)nullptr, (long long)n, (unsigned long long *)nullptr, (const uint4 *)env->net.d_wm[slot],
                            w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden, d_values, (const uint2 *)sv.u_info, sv.best,
                            (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0, &env->v.counters[C_ERR],
                            (unsigned long long)ERRF_DELTA);
     else
 #endif
     hipLaunchKernelGGL(eval_rows_delta_kernel, dim3((unsigned)dblocks), dim3(DELTA_THREADS), DELTA_LDS_TOTAL, s, (const uint4 *)sv.u_rows,
-                       (const unsigned long long *)nullptr, (long long)n, (unsigned long long *)nullptr, (const float4 *)env->d_wt[slot],
+                       (const unsigned long long *)nullptr, (long long)n, (unsigned long long *)nullptr, (const float4 *)env->net.d_wt[slot],
                        w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden, d_values, (const uint2 *)sv.u_info, sv.best,
                        (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0, &env->v.counters[C_ERR],
                        (unsigned long long)ERRF_DELTA, (const unsigned long long *)nullptr, 0ll);
