@@ -273,12 +273,19 @@ __global__ __launch_bounds__(SRCH_NT) void srch_reduce_kernel(long long n, const
         float v2;
         if (key & 0x80000000u) v2 = c_v1[j];
         else {
-            v2 = 0.0f;
+            // (sum over the doubles + 2 x sum over the other rolls) / 36, each in roll order.  A chain of fmaf with the fp32 weights
+            // 1/36 and 2/36 -- which add up to 1 + 2 ulp -- gave V2 = 1.0000002 when every reply was worth exactly 1.0; here equal
+            // replies of 1.0 or 0.0 give exactly that, and the average of values in [0, 1] stays inside [0, 1]
+            float sd = 0.0f, so = 0.0f;
             const float *r = rval + j * SRCH_ROLLS;
 #pragma unroll
             for (int idx = 0, a = 1; a <= 6; ++a)
 #pragma unroll
-                for (int d = a; d <= 6; ++d, ++idx) v2 = fmaf(a == d ? 1.0f / 36.0f : 2.0f / 36.0f, r[idx], v2);
+                for (int d = a; d <= 6; ++d, ++idx) {
+                    if (a == d) sd += r[idx];
+                    else so += r[idx];
+                }
+            v2 = (sd + 2.0f * so) * (1.0f / 36.0f);
         }
         c_v2[j] = v2;
         const unsigned long long pk = srch_pack(v2, key & 0x7FFFFFFFu, mover);

@@ -199,7 +199,9 @@ int bgamd_env_last_choice(bgamd_env *env, int32_t *d_chosen, int32_t *d_count, i
  *   4. V2(c) = v1(c) for a terminal c; otherwise  V2(c) = sum over the 21 unordered opponent rolls r = (1,1), (1,2), ..., (6,6), in that
  *      order, of w_r R(c, r), w_r = 1/36 for a double and 2/36 otherwise, where R(c, r) is the value of the reply the greedy step
  *      would choose from c (the opponent's turn bit, arg-min for PLAYER2 / arg-max for PLAYER1, no special case for terminal
- *      replies) -- or, when the opponent has no legal move, the net's value of c with the OPPONENT's turn bit;
+ *      replies) -- or, when the opponent has no legal move, the net's value of c with the OPPONENT's turn bit.  In fp32 the sum is formed
+ *      as (sum over the 6 doubles + 2 x sum over the 15 other rolls) / 36, each part in roll order: replies that are all exactly 1.0 (or
+ *      0.0) give exactly 1.0 (0.0), and V2 never leaves [0, 1];
  *   5. choose the kept c with the best V2 for the mover (ties: the smaller key), then apply / terminal check / flip or auto-reset
  *      exactly as the greedy step does;
  *   6. bgamd_env_last_choice: the chosen sequence, index and count (exact with BGAMD_WANT_INDEX), value = V2 of the choice.

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import random_boards as _random_boards
+from nets import forward_bf16_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -279,11 +280,6 @@ def test_values_vs_reference_model(bg, O, golden_dir, weights):
         assert np.abs(vv - g["v64"][idx]).max() < 1e-5, m
 
 
-def _bf16_round(x):
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)
-
-
 def test_bf16_mode_matches_bf16_emulation(bg, golden_dir, weights):
     """bf16 speed mode (v_mfma_f32_32x32x16_bf16): against an fp64 evaluation of the SAME bf16-rounded
     weights and features the kernel agrees to 2e-5; against the fp32 reference it is ~3e-4 (not a parity mode)."""
@@ -292,11 +288,7 @@ def test_bf16_mode_matches_bf16_emulation(bg, golden_dir, weights):
     env = bg.VecGame(1, arena_rows=1 << 20)
     env.load_weights(weights)
     v = _np(env.evaluate(g["states"].astype(np.int32), g["turn"], precision=bg.BF16))
-    W1 = _bf16_round(weights[:25344].reshape(128, 198)).astype(np.float64)
-    b1, W2, b2 = weights[25344:25472].astype(np.float64), weights[25472:25600].astype(np.float64), float(weights[25600])
-    X = _bf16_round(g4["X"]).astype(np.float64)
-    h = 1.0 / (1.0 + np.exp(-(X @ W1.T + b1)))
-    ref = 1.0 / (1.0 + np.exp(-(h @ W2 + b2)))
+    ref = forward_bf16_f64(weights, g4["X"])                 # (tests/nets.py: the same emulation serves the other weight tables)
     print("bf16: max |gpu - bf16 emulation| = %.3g, max |gpu - fp32 reference| = %.3g" % (np.abs(v - ref).max(), np.abs(v - g["v32"]).max()))
     assert np.abs(v - ref).max() < 2e-5
     assert np.abs(v - g["v32"]).max() < 5e-3
@@ -354,7 +346,9 @@ def test_bf16_mode_choice_agreement(bg, O, weights):
         assert abs(vv[k[0]] - best) < 5e-3
 
 
-def _check_greedy_step(O, w, pre, pt, dice, post, lanes):
+def _check_greedy_step(O, w, pre, pt, dice, post, lanes, strict=False):
+    """strict: the tie rule too -- the applied afterstate is the FIRST candidate in reference order among those whose fp64 value is the
+    best one (model.py:212-213: torch.argmax / argmin return the first index)."""
     for lane in lanes:
         s = O.State.from28(pre[lane], pt[lane])
         _, _, cand = O.evaluate_turn_sequences(s, int(pt[lane]), int(dice[lane, 0]), int(dice[lane, 1]))
@@ -366,6 +360,8 @@ def _check_greedy_step(O, w, pre, pt, dice, post, lanes):
         assert k, lane
         best = v.max() if pt[lane] == 0 else v.min()
         assert abs(v[k[0]] - best) < 1e-5, (lane, v[k[0]], best)
+        if strict:
+            assert k[0] == int(np.nonzero(v == best)[0][0]), (lane, k[0])
 
 
 def test_greedy_steps_value_optimal(bg, O, weights):
