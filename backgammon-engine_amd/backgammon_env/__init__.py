@@ -364,6 +364,20 @@ class VecGame:
         torch.cuda.current_stream().synchronize()
         return info, st, val
 
+    def choice_spread(self):
+        """Do the candidates of the last greedy step still differ?  (include/bgamd.h, bgamd_env_choice_spread: reduced on the device
+        over the rows unique_rows() lists.)  -> dict: count int32 [n] rows per lane, best / worst float32 [n] the extreme values from the
+        mover's side (0 where count is 0), tied int32 [n] rows bit-equal to best -- device tensors -- and the host numbers choice_lanes
+        (count >= 2), all_tied_lanes (of those: tied == count), rows, empty_lanes (count == 0).  Synchronises for the four numbers."""
+        cnt, tied = self._buf((self.n,), torch.int32), self._buf((self.n,), torch.int32)
+        best, worst = self._buf((self.n,), torch.float32), self._buf((self.n,), torch.float32)
+        summ = self._buf((4,), torch.int64)
+        _capi.check(self._lib.bgamd_env_choice_spread(self._h, _ptr(cnt), _ptr(best), _ptr(worst), _ptr(tied), _ptr(summ), _stream()),
+                    "choice_spread")
+        a, b, c, d = (int(x) for x in summ.cpu().tolist())
+        return {"count": cnt, "best": best, "worst": worst, "tied": tied, "choice_lanes": a, "all_tied_lanes": b, "rows": c,
+                "empty_lanes": d}
+
     def stats(self):
         out = (C.c_uint64 * 10)()
         _capi.check(self._lib.bgamd_env_stats(self._h, out), "stats")

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BGAMD_LIB") or os.path.join(os.path.dirname(_HERE), "libbgamd.so")
 
 OK = 0
+E_INVALID, E_WEIGHTS = -1, -8
 ROLL, AUTO_RESET, NO_FLIP, WANT_INDEX, ONLY_P1, ONLY_P2, WEIGHTS_SLOT1 = 1, 2, 4, 8, 16, 32, 64
 ROLLOUT_ROTATE = 128
 ROLLOUT_VR = 256
@@ -72,6 +73,8 @@ SYMBOLS = [
     ("bgamd_env_legal_moves", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("bgamd_env_unique_rows_info", C.c_int64, [_P, _P, C.c_int64, _P]),
     ("bgamd_env_unique_rows_read", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("bgamd_net_health", C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P]),
+    ("bgamd_env_choice_spread", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_set_trajectory", C.c_int, [_P, _P, C.c_int64]),
     ("bgamd_env_get_progress", C.c_int, [_P, _P, _P, _P]),
     ("bgamd_env_set_trajectory_ring", C.c_int, [_P, _P, C.c_int64, _P]),
@@ -110,6 +113,13 @@ SYMBOLS = [
     ("bgamd_td_time", C.c_int, [_P, C.c_int]),
     ("bgamd_td_times", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 ]
+
+
+class NetHealth(C.Structure):
+    """bgamd_net_health_t (include/bgamd.h), field for field"""
+    _fields_ = [("nonfinite", C.c_int64), ("rows", C.c_int64), ("saturated", C.c_int64), ("dead_units", C.c_int64),
+                ("max_abs", C.c_float * 4), ("max_abs_preact", C.c_float), ("v_min", C.c_float), ("v_max", C.c_float),
+                ("fits_f16_split", C.c_int32), ("unit_saturated", C.c_int32 * 128)]
 
 
 class BgamdError(RuntimeError):
@@ -156,4 +166,6 @@ def check(rc: int, what: str = ""):
     msg = lib.bgamd_error_string(int(rc)).decode()
     if rc == -2:
         msg += ": " + lib.bgamd_last_hip_error().decode()
-    raise BgamdError(f"{what or 'bgamd'} failed ({rc}): {msg}")
+    err = BgamdError(f"{what or 'bgamd'} failed ({rc}): {msg}")
+    err.code = int(rc)                    # the BGAMD_E_* value, for callers that handle one of them (E_WEIGHTS = -8)
+    raise err

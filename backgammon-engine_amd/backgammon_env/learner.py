@@ -288,6 +288,13 @@ class DeviceTDLambdaLearner:
     def state_dict(self):
         return TDLambdaLearner.state_dict(self)
 
+    def health(self, rows=None, threshold: float = 15.0):
+        """backgammon_env.health.net_health of the learner's own device weights as they stand on the current stream (no copy to the
+        host): non-finite count, largest |w| per tensor, whether an env would load the table, and on `rows` (int32 [..., 8] 32-byte
+        rows, e.g. health.health_rows of the round just replayed) the hidden layer's saturation."""
+        from . import health
+        return health.net_health(self.theta, rows, threshold)
+
     def time_trace_kernel(self, enable=True):
         self._capi.check(self._lib.bgamd_td_time(self._h, 1 if enable else 0), "td_time")
 
@@ -507,12 +514,14 @@ class DeviceTDLambdaLearner:
         return float(sq.value), int(cnt.value)
 
 
-def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, episode=None):
+def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, episode=None, probe=None):
     """One round of self-play from a frozen weight snapshot (train.py:527-547 semantics): every lane plays
     ONE game to the end, turns are logged. -> (rows [T, n, 8] int32, lengths [n], p1_won [n] bool).
     Round k of an env plays episode k of every lane (global game id lane_offset + lane + k * lane_stride): new dice,
     new opening roll and new exploration draws for every game, as play_game rolls fresh dice for every game
-    (train.py:64-121).  episode=None continues the env's own round counter; an explicit value replays that round."""
+    (train.py:64-121).  episode=None continues the env's own round counter; an explicit value replays that round.
+    probe: called once as probe(env) after the round's first 16 turns, while nearly every lane is still in its game (a read-only look
+    at a live step, e.g. env.choice_spread(): by the round's last step only the longest games are left)."""
     if episode is None:
         episode = getattr(env, "_round", 0)
     env._round = int(episode) + 1
@@ -523,6 +532,9 @@ def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, epi
         k = min(16, max_plies - done_steps)
         env.run_greedy(k, auto_reset=False, epsilon=epsilon, precision=precision)
         done_steps += k
+        if probe is not None:
+            probe(env)
+            probe = None
         if bool(((env.flags() & 4) != 0).all()):
             break
     flags = env.flags()

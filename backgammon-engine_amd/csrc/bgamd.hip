@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <string>
 #include <vector>
 #include <queue>
@@ -638,6 +639,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 #include "bg_search.h"
 #include "bg_rollout.h"
 #include "bg_vr.h"
+#include "bg_health.h"
 
 }  // namespace
 
@@ -835,6 +837,8 @@ struct bgamd_env {
     SearchState srch;
     RolloutState ro;
     PrerollState pre;
+    uint32_t *spread = nullptr;            // [5][n] per-lane words of bgamd_env_choice_spread (bg_health.h, SpreadView)
+    bool greedy_stepped = false;           // a greedy step has been issued on this env: the arenas hold its rows
 };
 
 namespace {
@@ -1056,6 +1060,7 @@ static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t
         HIPCHK(hipMalloc(&rv.task_off, n * 4));
         HIPCHK(hipMalloc(&rv.task_n, n * 4));
     }
+    HIPCHK(hipMalloc(&env->spread, (size_t)n_games * 5 * 4));
     HIPCHK(hipMemset(v.counters, 0, C_COUNT * 8));
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_f32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_TOTAL));
 #ifdef BGAMD_EXPERIMENTAL
@@ -1085,7 +1090,7 @@ int bgamd_env_destroy(bgamd_env *env)
     const StagedView &sv = env->sv;
     free_all({v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq, v.chosen_val, v.rows, v.seqs,
               v.values, v.counters, env->a_ctr, sv.root_rows, sv.root_hidden, sv.d1, sv.d2, sv.f, sv.f2, sv.u_rows, sv.u_info, sv.best,
-              env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n, env->d_scalar, env->d_tmp});
+              env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n, env->d_scalar, env->d_tmp, env->spread});
     for (hipEvent_t e : env->ev) hipEventDestroy(e);
     if (env->ev_fork) hipEventDestroy(env->ev_fork);
     if (env->ev_join) hipEventDestroy(env->ev_join);
@@ -1774,6 +1779,7 @@ int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision
     for (int64_t step = 0; step < n_steps; ++step) {
         rc = run.step(ss, step + 1 < n_steps);
         if (rc) return rc;
+        env->greedy_stepped = true;
     }
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
@@ -2240,6 +2246,66 @@ int bgamd_env_unique_rows_read(bgamd_env *env, int64_t first, int64_t n_rows, in
     hipLaunchKernelGGL(rows_values_kernel, grid1(n_rows, 128), dim3(128), 0, (hipStream_t)stream, (const uint4 *)env->sv.u_rows,
                        (const float *)env->v.values, (long long)first, (long long)n_rows, d_states28, d_values,
                        (const unsigned long long *)env->sv.tops, (long long)env->sv.b_base);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_choice_spread(bgamd_env *env, int32_t *d_count, float *d_best, float *d_worst, int32_t *d_tied, int64_t *d_summary,
+                            void *stream)
+{
+    ENV_GUARD(env);
+    if (!env->greedy_stepped) return BGAMD_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = env->v.n;
+    const SpreadView sp{env->spread, env->spread + n, env->spread + 2 * n, env->spread + 3 * n, env->spread + 4 * n};
+    HIPCHK(hipMemsetAsync(env->spread, 0, (size_t)n * 5 * 4, s));
+    HIPCHK(hipMemsetAsync(sp.lo, 0xFF, (size_t)n * 4, s));
+    if (d_summary) HIPCHK(hipMemsetAsync(d_summary, 0, 4 * 8, s));
+    // the walk of bgamd_env_unique_rows_read: the last step's counters, the arenas one after the other (bg_search.h)
+    const unsigned long long *tops = env->sv.tops;
+    const long long bb = env->sv.b_base, cap_rows = env->sv.cap_rows;
+    long long rblocks = (cap_rows + SRCH_NT - 1) / SRCH_NT;
+    const long long lim = 8ll * env->n_cu;
+    const dim3 rgrid((unsigned)(rblocks < 1 ? 1 : (rblocks > lim ? lim : rblocks)));
+    hipLaunchKernelGGL(spread_reduce_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, (const uint4 *)env->sv.u_rows,
+                       (const uint2 *)env->sv.u_info, (const float *)env->v.values, n, sp);
+    hipLaunchKernelGGL(spread_tied_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, (const uint4 *)env->sv.u_rows,
+                       (const uint2 *)env->sv.u_info, (const float *)env->v.values, n, sp);
+    hipLaunchKernelGGL(spread_finish_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, sp, d_count, d_best, d_worst, d_tied,
+                       (unsigned long long *)d_summary);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+static_assert(sizeof(bgamd_net_health_t) == sizeof(HealthOut) && offsetof(bgamd_net_health_t, max_abs) == offsetof(HealthOut, max_abs) &&
+              offsetof(bgamd_net_health_t, fits_f16_split) == offsetof(HealthOut, fits_f16_split) &&
+              offsetof(bgamd_net_health_t, unit_saturated) == offsetof(HealthOut, unit_saturated), "bgamd_net_health_t and its device image");
+
+int bgamd_net_health(const float *d_theta, const void *d_rows, int64_t n_rows, float threshold, bgamd_net_health_t *d_out, void *stream)
+{
+    // (unit_saturated is int32: a count per unit must fit)
+    if (!d_theta || !d_out || !(threshold > 0.0f) || n_rows < 0 || n_rows > 0x7FFFFFFFll || (n_rows > 0 && !d_rows)) return BGAMD_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    HealthOut *out = reinterpret_cast<HealthOut *>(d_out);
+    hipLaunchKernelGGL(health_weights_kernel, dim3(1), dim3(HEALTH_W_THREADS), 0, s, d_theta, (long long)n_rows, out);
+    if (n_rows > 0) {
+        // the device's CU count and the kernel's LDS opt-in: looked up once per device (the stores race only with equal values)
+        static std::atomic<int> cu_of[64];
+        int dev = 0, n_cu = 0;
+        HIPCHK(hipGetDevice(&dev));
+        if (dev >= 0 && dev < 64) n_cu = cu_of[dev].load(std::memory_order_acquire);
+        if (n_cu <= 0) {
+            HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+            HIPCHK(hipFuncSetAttribute((const void *)health_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HEALTH_LDS_TOTAL));
+            if (n_cu <= 0) n_cu = 256;
+            if (dev >= 0 && dev < 64) cu_of[dev].store(n_cu, std::memory_order_release);
+        }
+        long long blocks = ((n_rows + 31) / 32 + HEALTH_THREADS / 64 - 1) / (HEALTH_THREADS / 64);
+        blocks = blocks > n_cu ? n_cu : blocks;
+        hipLaunchKernelGGL(health_rows_kernel, dim3((unsigned)blocks), dim3(HEALTH_THREADS), HEALTH_LDS_TOTAL, s, d_theta, (const uint4 *)d_rows,
+                           (long long)n_rows, threshold, out);
+        hipLaunchKernelGGL(health_finish_kernel, dim3(1), dim3(N_HID), 0, s, out);
+    }
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }

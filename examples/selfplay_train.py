@@ -24,6 +24,7 @@ import torch  # noqa: E402
 
 import backgammon_env as bg  # noqa: E402
 from backgammon_env.arena import head_to_head  # noqa: E402
+from backgammon_env import _capi, health as nh  # noqa: E402
 from backgammon_env.learner import DeviceTDLambdaLearner, TDLambdaLearner, play_round  # noqa: E402
 
 
@@ -36,7 +37,45 @@ def xavier_init(seed=0):
     return torch.cat([xu(128, 198).flatten(), torch.zeros(128), xu(1, 128).flatten(), torch.zeros(1)]).numpy()
 
 
-def run_continuous(a, env, arena, L, group, world, prec, say, n_classic=0, t0=None, turns=0):
+class HealthGuard:
+    """The run's net health (backgammon_env.health): a line after every round / window, the check before the weights go back into the
+    env, and a loud stop -- round, turns replayed, games -- instead of a traceback when the table has diverged."""
+
+    MIN_CHOICE_LANES = 64
+
+    def __init__(self, a, L, say):
+        self.a, self.L, self.say = a, L, say
+
+    def stop(self, what, where):
+        print(f"STOPPED {where}: {what}", file=sys.stderr, flush=True)
+        sys.exit(3)
+
+    def after(self, rows, spread, where, early=None):
+        """rows: int32 [m, 8] rows of the round just played (or None), spread: env.choice_spread() of its last self-play step; early: the
+        same after the round's first 16 turns.  A classic round's last step has only its longest games left (0 - 232 of 65 536 lanes in
+        profiles/net_health_rounds.txt), so --max-all-tied-share checks `early` where there is one, and no share of fewer than
+        MIN_CHOICE_LANES lanes; a window's last step has every lane live and is checked as it is."""
+        h = nh.net_health(self.L.theta, rows if self.a.health_rows > 0 else None)
+        self.say(where + " " + nh.line(h, spread) + ("" if not early else "; after 16 turns %.4f of %d"
+                                                       % (nh.all_tied_share(early), early["choice_lanes"])), flush=True)
+        try:
+            nh.check(h, early or spread, self.a.max_saturated_share, self.a.max_all_tied_share, self.MIN_CHOICE_LANES)
+        except nh.NetHealthError as e:
+            self.stop(str(e), where)
+
+    def load(self, env, where):
+        """env.load_weights of the learner's table; BGAMD_E_WEIGHTS (a table the value net cannot hold) stops the run like a failed check"""
+        try:
+            env.load_weights(self.L.theta.cpu().numpy())
+        except bg.BgamdError as e:
+            if getattr(e, "code", 0) != _capi.E_WEIGHTS:
+                raise
+            h = nh.net_health(self.L.theta)
+            self.stop(f"load_weights refused the table (BGAMD_E_WEIGHTS): {h['nonfinite']} of 25601 weights are not finite, largest finite "
+                      f"|fc1.weight| {h['max_abs']['fc1.weight']:.6g}", where)
+
+
+def run_continuous(a, env, arena, L, group, world, prec, say, guard, n_classic=0, t0=None, turns=0):
     """--continuous [--pipeline-rounds]: windows of self-play on every lane, the games that ended in a window replayed streamed through
     --slots; pipelined, window w is played while window w - 1 is replayed (learner on its own stream and host thread)."""
     import threading
@@ -62,7 +101,7 @@ def run_continuous(a, env, arena, L, group, world, prec, say, n_classic=0, t0=No
 
     for b in range(a.burn_in_windows):                 # lanes out of step before the first window that counts (weights: the initial ones)
         if b == 0:
-            env.load_weights(L.theta.cpu().numpy())
+            guard.load(env, "burn-in")
         sp.play(a.window_steps, epsilon=a.eps if a.eps is not None else a.eps_start, precision=prec)
         sp.finished()
     held, held_all = None, 0                           # finished games held back until --min-window-games (per rank, summed over the ranks) have accumulated
@@ -75,13 +114,20 @@ def run_continuous(a, env, arena, L, group, world, prec, say, n_classic=0, t0=No
         eps = a.eps if a.eps is not None else a.eps_start + (a.eps_end - a.eps_start) * min(1.0, games_done / total_games)
         sg = a.scale_games if a.scale_warmup <= 0 else min(a.scale_games, a.scale_warmup * 2.0 ** (r + n_classic))
         scale = min(1.0, sg / (a.slots * world))
-        env.load_weights(L.theta.cpu().numpy())        # the weights the last finished replay left
+        guard.load(env, f"window {r + 1} ({games_done} games, {turns} turns replayed)")      # the weights the last finished replay left
         if a.pipeline_rounds and pending is not None:
             th = threading.Thread(target=replay, args=(pending, scale))
             th.start()
-        table = None
+        table, h_rows, spread = None, None, None
         if r < n_win:
             sp.play(a.window_steps, epsilon=eps, precision=prec)
+            spread = env.choice_spread()               # the window's last self-play step
+            if a.health_rows > 0:                      # rows of this window out of the ring, spread over at least 16 of its steps
+                s1 = env.trajectory_step()
+                k = min(a.window_steps, a.ring_steps, max(16, -(-a.health_rows // a.games)))
+                slots = sorted({(s1 - 1 - (i * a.window_steps) // k) % a.ring_steps for i in range(k)})
+                h_rows = sp.rows[slots].reshape(-1, 8)
+                h_rows = nh.thin(h_rows[(h_rows != 0).any(1)], a.health_rows).clone()      # (a slot no turn was logged to is all zero: no position)
             table = sp.finished(keep_margin=a.window_steps if a.pipeline_rounds else 0)
             dropped += sp.dropped
             n_fin = torch.tensor([int(table[0].numel())], dtype=torch.int64, device="cuda")
@@ -115,6 +161,8 @@ def run_continuous(a, env, arena, L, group, world, prec, say, n_classic=0, t0=No
                 f"{float(table[2].float().mean().item()) if table is not None and table[0].numel() else 0.0:.1f}), eps {eps:.3f}, " +
                 (f"td loss {res['out'][0] / max(1, res['out'][1]):.5f} over {res['out'][1]} turns, {world * turns / (time.time() - t0):.0f} turns/s" if res else "no replay yet"),
                 flush=True)
+        if r < n_win:                                  # (no learner thread is running here: the pipelined replay has been joined)
+            guard.after(h_rows, spread, f"window {r + 1} ({games_done} games, {turns} turns replayed)")
     torch.cuda.synchronize()
     say(f"{games_done} games, {turns} turns replayed per rank in {time.time() - t0:.2f} s; {dropped} games dropped (longer than the ring allows)", flush=True)
     w_after = L.theta.cpu().numpy()
@@ -176,6 +224,16 @@ def main():
     ap.add_argument("--in-library-collective", action="store_true", help="multi-rank: the per-step all-reduce is issued by the library on the "
                     "learner's stream (bgamd_td_replay_allreduce, an RCCL communicator of the learner's own) instead of torch.distributed per step")
     ap.add_argument("--host-learner", action="store_true", help="PyTorch closed-form replay instead of the HIP kernels")
+    ap.add_argument("--health-rows", type=int, default=65536, help="after every round / window the net's health is measured on about this many of "
+                    "its rows, spread evenly over all the round's turns (a window: over 16 of its steps) (bgamd_net_health: hidden units with "
+                    "|a| > 15) and printed with the weights' largest magnitudes; 0 = weights only")
+    ap.add_argument("--max-saturated-share", type=float, default=None, help="stop the run when more than this share of the (row, hidden unit) pairs is "
+                    "saturated (default: print only -- DESIGN §6 says why no default is set)")
+    ap.add_argument("--max-all-tied-share", type=float, default=0.5, help="stop the run when more than this share of the lanes with a choice gave every "
+                    "candidate the same value -- the tie rule is playing, not the net.  Checked on the step after a classic round's first 16 turns and "
+                    "on a window's last step (every lane is live there), never on fewer than 64 lanes.  0.5 is halfway between the healthy 0.0001 and "
+                    "the collapsed 1.0000 (DESIGN §6); 1 = print only")
+    ap.add_argument("--init-weights", default=None, help="start from this table (a file of 25 601 float32: W1 | b1 | W2 | b2) instead of xavier_init()")
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--precision", choices=("auto", "f32", "f16x2", "bf16"), default="auto",
                     help="value net of the self-play steps: f32 = incremental fp32; f16x2 = W1 as f16 hi+lo on the MFMA pipe (same "
@@ -200,12 +258,15 @@ def main():
     say = print if rank == 0 else (lambda *x, **k: None)
     prec = (bg.BF16 if a.precision == "bf16" else
             bg.F16X2 if a.precision == "f16x2" or (a.precision == "auto" and a.games < 16384) else bg.F32)
+    w0 = xavier_init() if a.init_weights is None else np.fromfile(a.init_weights, dtype=np.float32)
     if a.host_learner:
-        L = TDLambdaLearner(xavier_init(), device="cuda", alpha=0.1, lam=0.7)
+        L = TDLambdaLearner(w0, device="cuda", alpha=0.1, lam=0.7)
     else:
-        L = DeviceTDLambdaLearner(xavier_init(), max_games=a.games, alpha=0.1, lam=0.7)
+        L = DeviceTDLambdaLearner(w0, max_games=a.games, alpha=0.1, lam=0.7)
     if a.in_library_collective and not a.host_learner:
         L.init_collective(group)
+    guard = HealthGuard(a, L, say)
+    guard.after(None, None, "start (0 games)")           # the starting table: the arena below loads it
     say("before: vs random", head_to_head(arena, L.theta.cpu().numpy(), None)["win_rate"], flush=True)
     t0, turns = time.time(), 0
     total_games = a.rounds * a.games * world
@@ -220,8 +281,11 @@ def main():
             L.lambda_decay = a.lam
         # linear decay of the exploration rate across the run (train.py:531)
         eps = a.eps if a.eps is not None else a.eps_start + (a.eps_end - a.eps_start) * (games_done / total_games)
-        env.load_weights(L.theta.cpu().numpy())
-        rows, lengths, p1_won = play_round(env, max_plies=a.max_plies, epsilon=eps, precision=prec)   # round r = episode r: fresh dice
+        guard.load(env, f"round {r + 1} ({games_done} games, {turns} turns replayed)")
+        early = {}
+        rows, lengths, p1_won = play_round(env, max_plies=a.max_plies, epsilon=eps, precision=prec,     # round r = episode r: fresh dice
+                                           probe=lambda e: early.update(e.choice_spread()))
+        spread = env.choice_spread()                         # the round's last self-play step
         if r < 2:                                            # every round must play NEW games
             d = env.dice().clone()
             assert first_dice is None or not torch.equal(d, first_dice), "two rounds rolled the same dice"
@@ -234,11 +298,14 @@ def main():
         else:
             sq, cnt = L.replay_rows(rows, lengths, p1_won, group=group, batch_scale=scale, sub_round=a.sub_round, slots=a.slots)
         turns += cnt
+        h_rows = nh.round_rows(rows, lengths, a.health_rows) if a.health_rows > 0 else None      # spread over all the round's turns
+        guard.after(h_rows, spread,
+                    f"round {r + 1} ({(r + 1) * a.games * world} games, {turns} turns replayed)", early)
         if a.verbose or r % 20 == 19 or r == a.rounds - 1:
             say(f"round {r + 1}: {(r + 1) * a.games * world} games, mean len {cnt / a.games:.1f}, td loss {sq / cnt:.5f}, "
                 f"{world * turns / (time.time() - t0):.0f} turns/s", flush=True)
     if a.continuous:
-        return run_continuous(a, env, arena, L, group, world, prec, say, n_classic, t0, turns)
+        return run_continuous(a, env, arena, L, group, world, prec, say, guard, n_classic, t0, turns)
     w_after = L.theta.cpu().numpy()
     if world > 1:                                             # the replicas must still hold the same weights
         chk = torch.tensor([float(np.abs(w_after).sum()), -float(np.abs(w_after).sum())], dtype=torch.float64, device="cuda")

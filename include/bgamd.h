@@ -323,6 +323,47 @@ int64_t bgamd_env_unique_rows_info(bgamd_env *env, void *d_info /* uint32[cap][2
 int bgamd_env_unique_rows_read(bgamd_env *env, int64_t first, int64_t n_rows, int32_t *d_states28, float *d_values,
                                void *stream);
 
+/* ---- net health: is this weight table still one the value net can play with, and does its hidden layer still tell rows apart? ----------
+ * A training loop's own question (the reference's loop never asks it: train.py:519-547 saves whatever the updates left).  Stateless, in
+ * the style of bgamd_encode_rows: d_theta = 25 601 device floats (W1[128][198] | b1 | W2 | b2: a learner's table as it stands, no env
+ * needed), d_rows = n_rows 32-byte rows (16-byte aligned) in the trajectory log's format (bgamd_pack_rows, bgamd_env_set_trajectory, the
+ * ring log), threshold > 0 (15: sigmoid'(15) ~ 3e-7, a unit that far out passes no gradient and tells no two rows apart).
+ *   weights : nonfinite = the NaN / +-Inf among the 25 601; max_abs = the largest finite |w| of each tensor, exact; fits_f16_split = 1
+ *             iff bgamd_weights_check (and so bgamd_env_load_weights) would accept the table -- the same test, run on the device;
+ *   rows    : a = fc1.weight x + fc1.bias of every row and unit in fp32 (the dense evaluator's v_mfma_f32_32x32x2_f32 chain over all 99
+ *             k-steps, W1 as it is: no 16-bit table), then the sigmoids and the second layer.  saturated = (row, unit) pairs with
+ *             |a| > threshold, unit_saturated[u] = the rows on which unit u is, dead_units = units that are on EVERY row,
+ *             max_abs_preact = max |a|, v_min / v_max = the extreme net outputs.
+ * n_rows = 0 (d_rows may be NULL): the weight fields, everything else zero.  The rows' fields mean something only when nonfinite == 0;
+ * with non-finite weights the call still completes.  Every field is an integer count or a min / max: bit-identical from call to call.
+ * threshold <= 0 (or NaN), n_rows < 0 or n_rows >= 2^31: BGAMD_E_INVALID.  Stream-ordered on the current device, nothing synchronises;
+ * d_out is DEVICE memory. */
+typedef struct {
+    int64_t nonfinite;            /* weights that are NaN or +-Inf, of 25 601 */
+    int64_t rows;                 /* n_rows */
+    int64_t saturated;            /* (row, unit) pairs with |a| > threshold, a = fc1.weight x + fc1.bias in fp32 */
+    int64_t dead_units;           /* units saturated on EVERY row (0 when n_rows = 0) */
+    float   max_abs[4];           /* largest finite |w| of fc1.weight, fc1.bias, fc2.weight, fc2.bias (0 if none finite) */
+    float   max_abs_preact;       /* max |a| over all pairs */
+    float   v_min, v_max;         /* smallest / largest net output over the rows */
+    int32_t fits_f16_split;       /* 1 iff bgamd_weights_check would accept this table */
+    int32_t unit_saturated[128];  /* per hidden unit: rows on which it is saturated */
+} bgamd_net_health_t;
+int bgamd_net_health(const float *d_theta /*25601*/, const void *d_rows /*n_rows x 32 B*/, int64_t n_rows, float threshold,
+                     bgamd_net_health_t *d_out, void *stream);
+
+/* ---- choice spread: do the candidates of a turn still differ? ------------------------------------------------------------------------
+ * Per lane, over exactly the rows bgamd_env_unique_rows_info / _read list for the last greedy step (copies still in that list count as
+ * rows), without copying a row to the host: d_count[n] = the lane's rows; d_best[n] / d_worst[n] = the extreme values from the MOVER's
+ * side, as stored (the mover is the row's turn bit; PLAYER1 plays the maximum, PLAYER2 the minimum -- the greedy step's rule, model.py:
+ * 205-213); d_tied[n] = rows whose value is bit-equal to best.  A lane without rows (finished, frozen, left out by BGAMD_ONLY_P1/P2, or
+ * without a legal move) reports count 0, best = worst = 0, tied 0.  With epsilon = 0, best is bit-equal to bgamd_env_last_choice's value
+ * wherever count >= 1.  d_summary[4] = lanes with count >= 2, of those the lanes with tied == count (the tie rule alone chose the move),
+ * total rows, lanes with count == 0.  Any pointer may be NULL.  A segmented reduction over the four arenas by game id; stream-ordered,
+ * no side effect on the env (its per-lane scratch words aside).  Before the first greedy step: BGAMD_E_INVALID. */
+int bgamd_env_choice_spread(bgamd_env *env, int32_t *d_count, float *d_best, float *d_worst, int32_t *d_tied,
+                            int64_t *d_summary /*[4]*/, void *stream);
+
 /* ---- trajectory log for the learner (the list of encodings play_game returns, train.py:105-106,
  * kept as 32-byte rows: 8 bit planes, turn of the side to move in plane 0 bit 31).  When set, every
  * greedy step stores the PRE-move row of each live lane at d_rows[(ply*n + lane)*32 B]; plies >=
