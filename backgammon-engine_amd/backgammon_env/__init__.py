@@ -29,7 +29,7 @@ from . import _capi
 from ._capi import (AUTO_RESET, BF16, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1, ONLY_P2, ROLL, ROLLOUT_ROTATE, ROLLOUT_VR,  # noqa: F401
                     WANT_INDEX, WEIGHTS_SLOT1, BgamdError)
 
-__all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "BgamdError", "set_seed", "pack_rows"]
+__all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "BgamdError", "set_seed", "pack_rows", "outcomes"]
 
 ERR_MESSAGES = {                                   # cppsrc/game.cpp:585-642, in source order
     0: "", 1: "Invalid origin", 2: "Origin out of range", 3: "Destination out of range",
@@ -69,6 +69,18 @@ def pack_rows(states28, turn, device="cuda"):
     out = torch.empty((n, 8), dtype=torch.int32, device=st.device)
     _capi.check(_capi.load().bgamd_pack_rows(_ptr(st), _ptr(t), n, _ptr(out), _stream()), "pack_rows")
     return out.reshape(*lead, 8)
+
+
+def outcomes(states28, device="cuda"):
+    """[..., 28] reference-layout states -> int32 [...] points from PLAYER1's side (include/bgamd.h, bgamd_outcomes): 0 = not over,
+    +1 / +2 / +3 = PLAYER1 won a single game / a gammon / a backgammon, -1 / -2 / -3 = PLAYER2 did; a state with |count| > 15 gives
+    _capi.OUTCOME_BAD."""
+    st = torch.as_tensor(states28, dtype=torch.int32).to(device).contiguous()
+    lead = st.shape[:-1]
+    n = st.numel() // 28
+    out = torch.empty((n,), dtype=torch.int32, device=st.device)
+    _capi.check(_capi.load().bgamd_outcomes(_ptr(st), n, _ptr(out), _stream()), "outcomes")
+    return out.reshape(lead)
 
 
 class PlayerType(enum.IntEnum):                    # bindings.cpp:46-48 (unscoped enum: equals ints)
@@ -119,6 +131,7 @@ class VecGame:
                                                lane_stride or 0, arena_rows), "bgamd_env_create")
         self._h = h
         self._has_weights = False
+        self._rollout_shape = (0, 0)       # P, T of the last rollout (rollout_outcomes_read)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -181,6 +194,13 @@ class VecGame:
         f = self._buf((self.n,), torch.int32)
         _capi.check(self._lib.bgamd_env_get_flags(self._h, _ptr(f), _stream()), "get_flags")
         return f
+
+    def outcomes(self):
+        """int32 [n]: the points of every lane's CURRENT board from PLAYER1's side (bgamd_env_outcomes) -- +-1 single game, +-2 gammon,
+        +-3 backgammon for a lane frozen on its final board (finished without auto_reset); 0 for a lane still playing or auto-reset."""
+        o = self._buf((self.n,), torch.int32)
+        _capi.check(self._lib.bgamd_env_outcomes(self._h, _ptr(o), _stream()), "outcomes")
+        return o
 
     def snapshot(self):
         """int32 [n, 32] = state28 | turn | die1 | die2 | flags: every scalar getter's data in one launch."""
@@ -297,7 +317,7 @@ class VecGame:
         return f, m
 
     def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
-                per_trial=False, variance_reduction=False):
+                per_trial=False, variance_reduction=False, outcomes=False):
         """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
         move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
         trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
@@ -305,7 +325,11 @@ class VecGame:
         wins), stderr [P], turns [P] (int64), truncated [P] (int32); per_trial: also trial_value [P, T] (float32), trial_turns [P, T].
         variance_reduction: also the luck-adjusted vr_mean [P] and vr_stderr [P] (float64; BGAMD_ROLLOUT_VR: every turn's luck against
         the pre-roll evaluation is subtracted from the trial's value), with per_trial trial_luck [P, T] (float64); the plain outputs are
-        the same as without it."""
+        the same as without it.
+        outcomes: also the games in points (bgamd_env_rollout_outcomes_read) -- counts [P, 6] (int64: trials that ended as PLAYER1 single
+        game, gammon, backgammon, PLAYER2 single game, gammon, backgammon; truncated trials are in none), equity [P] and equity_stderr [P]
+        (float64, PLAYER1's cubeless equity in points; a truncated trial counts 2 x - 1 of its net value x), with per_trial trial_points
+        [P, T] (int8, 0 = truncated).  The other outputs are the same as without it."""
         st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
         P, T = st.shape[0], int(trials)
         t = self._dev(turn, torch.int32, (P,))
@@ -319,12 +343,28 @@ class VecGame:
                                                 int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
                                                 _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
                                                 _ptr(out.get("trial_turns")), _stream()), "rollout")
+        self._rollout_shape = (P, T)
         if variance_reduction:
             out["vr_mean"], out["vr_stderr"] = self._buf((P,), torch.float64), self._buf((P,), torch.float64)
             if per_trial:
                 out["trial_luck"] = self._buf((P, T), torch.float64)
             _capi.check(self._lib.bgamd_env_rollout_vr_read(self._h, _ptr(out["vr_mean"]), _ptr(out["vr_stderr"]),
                                                             _ptr(out.get("trial_luck")), _stream()), "rollout_vr_read")
+        if outcomes:
+            out.update(self.rollout_outcomes_read(per_trial=per_trial))
+        return out
+
+    def rollout_outcomes_read(self, per_trial=False):
+        """The last rollout's games in points (bgamd_env_rollout_outcomes_read; raises before the first rollout) -> dict: counts [P, 6],
+        equity [P], equity_stderr [P], per_trial: trial_points [P, T] -- see rollout(outcomes=True)."""
+        P, T = self._rollout_shape
+        out = {"counts": self._buf((P, 6), torch.int64), "equity": self._buf((P,), torch.float64),
+               "equity_stderr": self._buf((P,), torch.float64)}
+        if per_trial:
+            out["trial_points"] = self._buf((P, T), torch.int8)
+        _capi.check(self._lib.bgamd_env_rollout_outcomes_read(self._h, _ptr(out["counts"]), _ptr(out["equity"]),
+                                                              _ptr(out["equity_stderr"]), _ptr(out.get("trial_points")), _stream()),
+                    "rollout_outcomes_read")
         return out
 
     def rollout_info(self):

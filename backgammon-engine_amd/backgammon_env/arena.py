@@ -11,7 +11,9 @@ from . import F32, VecGame
 
 def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
     """policies: ("net", slot), ("search", slot, top_k) or ("random",).  The constructor seats the first mover by game parity
-    (`Game(i % 2)`, train.py:265), no opening roll."""
+    (`Game(i % 2)`, train.py:265), no opening roll.
+    -> (games finished, PLAYER1 wins, points int64 [7]: lanes by VecGame.outcomes() + 3, i.e. PLAYER2 backgammon, gammon, single game,
+    not finished, PLAYER1 single game, gammon, backgammon)"""
     env.reset()
     env.set_states(None, torch.arange(env.n, dtype=torch.int32) % 2)
     for t in range(max_turns):
@@ -27,7 +29,8 @@ def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
     f = env.flags()
     done = (f & 4) != 0
     p1_won = done & (((f >> 1) & 1) == 0)
-    return int(done.sum()), int(p1_won.sum())
+    pts = torch.bincount((env.outcomes() + 3).to(torch.int64), minlength=7).cpu().tolist()
+    return int(done.sum()), int(p1_won.sum()), pts
 
 
 def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000, precision=F32, plies_a: int = 1, plies_b: int = 1,
@@ -35,7 +38,9 @@ def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000,
     """Win rate of A vs B (B = None: a uniformly random mover), sides alternated 50/50 as in
     evaluate_parallel (train.py:296-302): every lane plays one game with A as PLAYER1 and one with A as
     PLAYER2.  plies_a / plies_b = 2: that side moves by the 2-ply search (VecGame.step_search, top_k candidates, fp32 net).
-    -> dict(games, a_wins, win_rate)."""
+    -> dict(games, a_wins, win_rate, a_as_p1, a_as_p2) and the match in points (a single game 1, a gammon 2, a backgammon 3;
+    include/bgamd.h, bgamd_env_outcomes): a_points (A's points minus B's over both passes; a lane not finished at max_turns gives 0),
+    ppg (a_points / games), a_gammons, a_backgammons, b_gammons, b_backgammons (games won by that much)."""
     if plies_a not in (1, 2) or plies_b not in (1, 2):
         raise ValueError("plies must be 1 or 2")
     if plies_b == 2 and weights_b is None:
@@ -45,8 +50,12 @@ def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000,
         env.load_weights(weights_b, slot=1)
     a = ("net", 0) if plies_a == 1 else ("search", 0, top_k)
     b = (("net", 1) if plies_b == 1 else ("search", 1, top_k)) if weights_b is not None else ("random",)
-    n1, w1 = _play(env, a, b, max_turns, precision)          # A is PLAYER1
-    n2, w2 = _play(env, b, a, max_turns, precision)          # A is PLAYER2
+    n1, w1, h1 = _play(env, a, b, max_turns, precision)      # A is PLAYER1
+    n2, w2, h2 = _play(env, b, a, max_turns, precision)      # A is PLAYER2
     a_wins = w1 + (n2 - w2)
+    h = [x + y for x, y in zip(h1, reversed(h2))]            # from A's side: the second pass sign-flipped
+    a_points = sum((k - 3) * c for k, c in enumerate(h))
     return {"games": n1 + n2, "a_wins": a_wins, "win_rate": a_wins / max(n1 + n2, 1),
-            "a_as_p1": (n1, w1), "a_as_p2": (n2, n2 - w2)}
+            "a_as_p1": (n1, w1), "a_as_p2": (n2, n2 - w2),
+            "a_points": a_points, "ppg": a_points / max(n1 + n2, 1),
+            "a_gammons": h[5], "a_backgammons": h[6], "b_gammons": h[1], "b_backgammons": h[0]}

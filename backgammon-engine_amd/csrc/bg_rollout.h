@@ -9,11 +9,15 @@
 //             (launch_eval, what bgamd_evaluate_slot runs) and ro_trunc_scatter; between refills the greedy step's own kernels play
 //             R turns of every lane (GreedyRun), R dividing the turns a trial has left at its start when M > 0
 //   reduce    ro_reduce (wave per position)    : mean, stderr, turns, truncated in a fixed order; per-trial outputs
+//   outcomes  ro_outcome_reduce (wave per position, launched by bgamd_env_rollout_outcomes_read) : every trial's points
+//             (outcome_points of the board it was scored from, bg_outcome.h; 0 = truncated) -> the six counts and the equity
 #pragma once
 
 constexpr int RO_NT = 256;
 constexpr uint32_t RO_NONE = 0xFFFFFFFFu;            // lane_trial of a lane without a trial
 constexpr uint32_t RO_TRUNC = 1u << 30;              // internal trial_turns: the trial was scored by the net
+constexpr int RO_PTS_SHIFT = 17;                     // internal trial_turns, bits 17..19: the trial's points (outcome_points, bg_outcome.h) as a
+constexpr uint32_t RO_TURN_MASK = (1u << RO_PTS_SHIFT) - 1u;   // 3-bit two's complement, 0 = truncated; the turns (<= RO_TURN_LIMIT + 1 < 2^17) below
 constexpr uint32_t RO_TURN_LIMIT = 100000;           // M = 0: a trial still running after this many turns is an error
 enum { RO_NEXT = 0, RO_DONE = 1, RO_NTRUNC = 2, RO_ERR = 3, RO_CTRS = 4 };
 enum { ERRF_RO_LONG = 8, ERRF_RO_PLY = 16 };
@@ -27,7 +31,7 @@ struct RoView {
     const float *fan_val;                             // [P * F] (M == 1 only)
     uint32_t *lane_trial;                             // [L]
     float *t_val;                                     // [N]
-    uint32_t *t_turns;                                // [N] turns | RO_TRUNC
+    uint32_t *t_turns;                                // [N] turns | points << RO_PTS_SHIFT | RO_TRUNC
     uint4 *trows;                                     // [L][2] truncated trials of this refill
     uint32_t *tids;                                   // [L]
     unsigned long long *ctr;                          // RO_*
@@ -58,6 +62,13 @@ __device__ __forceinline__ unsigned long long ro_block_alloc(bool want, unsigned
     *tot = all;
     return base + before + rank;
 }
+
+// a scored trial's word: its turns and the points of the board it was scored from, in the one store the turns always took
+__device__ __forceinline__ uint32_t ro_turns_word(uint32_t turns, const uint32_t (&p)[8])
+{
+    return turns | (((uint32_t)outcome_points(p) & 7u) << RO_PTS_SHIFT);
+}
+__device__ __forceinline__ int ro_word_points(uint32_t w) { return (int)(w << (29 - RO_PTS_SHIFT)) >> 29; }
 
 __device__ __forceinline__ void ro_row(const uint32_t (&p)[8], int turn, uint4 *dst)
 {
@@ -100,8 +111,9 @@ __global__ __launch_bounds__(RO_NT) void ro_fan_collect_kernel(EnvView e, long l
 }
 
 // Refill point.  Lane g: a frozen lane's trial ended (1.0 if PLAYER1 won, turns = ply + 1: finish_turn does not advance the ply of a
-// game's last turn); a live lane at ply M is truncated (its row goes to the compact list, scored after this launch).  A lane without a
-// trial then takes the next unstarted one, trial jl = p T + i: at ply 0 from position p, or -- rotation -- at ply 1 from fan entry
+// game's last turn); a live lane at ply M is truncated (its row goes to the compact list, scored after this launch).  Every place that
+// scores a trial from a board also records its points (single game / gammon / backgammon) above the turns; a truncated trial's are 0.
+// A lane without a trial then takes the next unstarted one, trial jl = p T + i: at ply 0 from position p, or -- rotation -- at ply 1 from fan entry
 // p F + i % 36.  Trials that are over before a turn is played on a lane (a finished position: 0 turns; rotation: a first turn that
 // ended the game, or M = 1) are scored here and the lane takes the next.  The lane plays trial jl as episode jl + L - g with lane_stride 1
 // and lane_offset = base - L: game id base + jl, the dice of trial j = base + jl at every ply.
@@ -118,7 +130,7 @@ __global__ __launch_bounds__(RO_NT) void ro_refill_kernel(EnvView e, RoView r)
         const uint32_t meta = e.meta[g], ply = e.ply[g];
         if (meta & META_FINISHED) {
             r.t_val[j] = over_code(p) == 1 ? 1.0f : 0.0f;
-            r.t_turns[j] = ply + 1u;
+            r.t_turns[j] = ro_turns_word(ply + 1u, p);
             ++done;
         } else if (r.M > 0 && (long long)ply >= r.M) {
             if ((long long)ply > r.M) err |= ERRF_RO_PLY;
@@ -159,7 +171,7 @@ __global__ __launch_bounds__(RO_NT) void ro_refill_kernel(EnvView e, RoView r)
         }
         if (oc) {                                              // over before this lane plays a turn of it
             r.t_val[jl] = oc == 1 ? 1.0f : 0.0f;
-            r.t_turns[jl] = ply;
+            r.t_turns[jl] = ro_turns_word(ply, p);
             ++done;
             continue;
         }
@@ -218,10 +230,10 @@ __global__ __launch_bounds__(64) void ro_reduce_kernel(long long T, const float 
         const float x = t_val[base + i];
         const uint32_t w = t_turns[base + i];
         s += (double)x;
-        ts += w & (RO_TRUNC - 1u);
+        ts += w & RO_TURN_MASK;
         tr += (w & RO_TRUNC) ? 1u : 0u;
         if (o_val) o_val[base + i] = x;
-        if (o_turns) o_turns[base + i] = (int32_t)(w & (RO_TRUNC - 1u));
+        if (o_turns) o_turns[base + i] = (int32_t)(w & RO_TURN_MASK);
     }
     const double m = ro_wave_sum(s) / (double)T;
     double q = 0.0;
@@ -242,5 +254,51 @@ __global__ __launch_bounds__(64) void ro_reduce_kernel(long long T, const float 
         if (serr) serr[p] = T > 1 ? sqrt(q / ((double)T * (double)(T - 1))) : 0.0;
         if (turns) turns[p] = (int64_t)t64;
         if (truncated) truncated[p] = (int32_t)trs;
+    }
+}
+
+// Outcomes of the trials, wave per position in ro_reduce_kernel's order (lane i takes trials i, i + 64, ...; the same butterfly; lane 0
+// writes).  counts[p][6]: PLAYER1 single / gammon / backgammon, PLAYER2 single / gammon / backgammon.  Equity of a trial in points:
+// its points when it was played out, 2 x - 1 of its fp32 net value x when it was truncated (the net knows wins only).
+template <int LAST>                                   // (a template for its place in the code object: bg_outcome.h)
+__global__ __launch_bounds__(64) void ro_outcome_reduce_kernel(long long T, const float *__restrict__ t_val, const uint32_t *__restrict__ t_turns,
+                                                               int64_t *__restrict__ counts, double *__restrict__ equity,
+                                                               double *__restrict__ eq_serr, int8_t *__restrict__ o_pts)
+{
+    const long long p = blockIdx.x, base = p * T;
+    const int lane = threadIdx.x;
+    auto eq = [&](long long i) -> double {
+        const int w = ro_word_points(t_turns[base + i]);
+        return w ? (double)w : 2.0 * (double)t_val[base + i] - 1.0;
+    };
+    double s = 0.0;
+    uint32_t c[6] = {0, 0, 0, 0, 0, 0};
+    for (long long i = lane; i < T; i += 64) {
+        const int w = ro_word_points(t_turns[base + i]);
+        s += eq(i);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            c[k] += w == k + 1 ? 1u : 0u;
+            c[3 + k] += w == -(k + 1) ? 1u : 0u;
+        }
+        if (o_pts) o_pts[base + i] = (int8_t)w;
+    }
+    const double m = ro_wave_sum(s) / (double)T;
+    double q = 0.0;
+    for (long long i = lane; i < T; i += 64) {
+        const double d = eq(i) - m;
+        q += d * d;
+    }
+    q = ro_wave_sum(q);
+    unsigned long long cs[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cs[k] = wave_sum_u32(c[k]);
+    if (lane == 0) {
+        if (counts) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) counts[p * 6 + k] = (int64_t)cs[k];
+        }
+        if (equity) equity[p] = m;
+        if (eq_serr) eq_serr[p] = T > 1 ? sqrt(q / ((double)T * (double)(T - 1))) : 0.0;
     }
 }

@@ -637,6 +637,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 #include "bg_staged_kernels.h"
 #include "bg_random_kernels.h"
 #include "bg_search.h"
+#include "bg_outcome.h"
 #include "bg_rollout.h"
 #include "bg_vr.h"
 #include "bg_health.h"
@@ -755,6 +756,7 @@ struct RolloutState {
     float *vf = nullptr, *f0 = nullptr;                            // vf [L][21]: the trial lanes' f of the turn at hand
     long long cap_vtrials = 0, cap_vlanes = 0, cap_vpos = 0;
     long long vr_P = 0, vr_T = 0;          // P, T of the last rollout if it had BGAMD_ROLLOUT_VR (0: bgamd_env_rollout_vr_read refuses)
+    long long out_P = 0, out_T = 0;        // P, T of the last rollout (0: none yet, or it failed: bgamd_env_rollout_outcomes_read refuses)
     int read_back_ready()                  // the pinned words and the two events, created on first use
     {
         if (!host) HIPCHK(hipHostMalloc(&host, 8 * 8));
@@ -1997,6 +1999,7 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
                       float *d_trial_value, int32_t *d_trial_turns, void *stream)
 {
     if (env) env->ro.vr_P = 0;                         // (bgamd_env_rollout_vr_read: only after a call that had the flag)
+    if (env) env->ro.out_P = 0;                        // (bgamd_env_rollout_outcomes_read: only after a call that succeeded)
     if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
     if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1 | BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
     if (n_positions >= (1ll << 31) || trials >= (1ll << 31) || n_positions * trials >= (1ll << 31) || lanes > (1ll << 30))
@@ -2144,6 +2147,7 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     if (vr) { ro.vr_P = P; ro.vr_T = T; }
+    ro.out_P = P; ro.out_T = T;
     return BGAMD_OK;
 }
 
@@ -2160,6 +2164,35 @@ int bgamd_env_rollout_vr_read(bgamd_env *env, double *d_vr_mean, double *d_vr_st
     if (env->ro.vr_P < 1) return BGAMD_E_INVALID;
     hipLaunchKernelGGL(ro_vr_reduce_kernel, dim3((unsigned)env->ro.vr_P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.vr_T,
                        (const float *)env->ro.tval, (const double *)env->ro.tluck, d_vr_mean, d_vr_stderr, d_trial_luck);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_outcomes_read(bgamd_env *env, int64_t *d_counts, double *d_equity, double *d_equity_stderr,
+                                    int8_t *d_trial_points, void *stream)
+{
+    ENV_GUARD(env);
+    if (env->ro.out_P < 1) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL((ro_outcome_reduce_kernel<0>), dim3((unsigned)env->ro.out_P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.out_T,
+                       (const float *)env->ro.tval, (const uint32_t *)env->ro.tturns, d_counts, d_equity, d_equity_stderr, d_trial_points);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+// ---- points of finished games (bg_outcome.h) ---------------------------------------------------------------------------------
+int bgamd_outcomes(const int32_t *d_states28, int64_t n, int32_t *d_points, void *stream)
+{
+    if (!d_states28 || !d_points || n < 1) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL((outcomes_kernel<0>), grid1(n, 256), dim3(256), 0, (hipStream_t)stream, d_states28, (long long)n, d_points);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_outcomes(bgamd_env *env, int32_t *d_points, void *stream)
+{
+    ENV_GUARD(env);
+    if (!d_points) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL((env_outcomes_kernel<0>), grid1(env->v.n, 256), dim3(256), 0, (hipStream_t)stream, env->v, d_points);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }

@@ -37,6 +37,13 @@ def xavier_init(seed=0):
     return torch.cat([xu(128, 198).flatten(), torch.zeros(128), xu(1, 128).flatten(), torch.zeros(1)]).numpy()
 
 
+def say_arena(say, label, r):
+    """The arena line as it always was (games, wins, win rate, the two passes), then the same match in points per game."""
+    say(label, {k: r[k] for k in ("games", "a_wins", "win_rate", "a_as_p1", "a_as_p2")}, flush=True)
+    say(f"{label} in points: {r['ppg']:+.4f} per game ({r['a_points']:+d} over {r['games']} games; gammons {r['a_gammons']} : "
+        f"{r['b_gammons']}, backgammons {r['a_backgammons']} : {r['b_backgammons']})", flush=True)
+
+
 class HealthGuard:
     """The run's net health (backgammon_env.health): a line after every round / window, the check before the weights go back into the
     env, and a loud stop -- round, turns replayed, games -- instead of a traceback when the table has diverged."""
@@ -171,10 +178,10 @@ def run_continuous(a, env, arena, L, group, world, prec, say, guard, n_classic=0
         dist.all_reduce(chk, op=dist.ReduceOp.MAX, group=group)
         assert chk[0].item() == -chk[1].item(), "replicas diverged"
         say("replicas identical across", world, "ranks")
-    say("after: vs random", head_to_head(arena, w_after, None), flush=True)
+    say_arena(say, "after: vs random", head_to_head(arena, w_after, None))
     ref = os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32")
     if os.path.exists(ref):
-        say("after: vs tdgammonNEW100k", head_to_head(arena, w_after, np.fromfile(ref, dtype=np.float32)), flush=True)
+        say_arena(say, "after: vs tdgammonNEW100k", head_to_head(arena, w_after, np.fromfile(ref, dtype=np.float32)))
     if world > 1:
         dist.destroy_process_group()
 
@@ -312,10 +319,10 @@ def main():
         dist.all_reduce(chk, op=dist.ReduceOp.MAX, group=group)
         assert chk[0].item() == -chk[1].item(), "replicas diverged"
         say("replicas identical across", world, "ranks")
-    say("after: vs random", head_to_head(arena, w_after, None), flush=True)
+    say_arena(say, "after: vs random", head_to_head(arena, w_after, None))
     ref = os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32")       # the reference's own 100k-episode checkpoint
     if os.path.exists(ref):
-        say("after: vs tdgammonNEW100k", head_to_head(arena, w_after, np.fromfile(ref, dtype=np.float32)), flush=True)
+        say_arena(say, "after: vs tdgammonNEW100k", head_to_head(arena, w_after, np.fromfile(ref, dtype=np.float32)))
     if world > 1:
         dist.destroy_process_group()
 

@@ -217,7 +217,7 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream);
  * the first search step. */
 int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream);
 
-/* ---- Monte Carlo rollouts (TD-Gammon / GNU Backgammon rollouts, win/loss only) --------------------------------------------------------
+/* ---- Monte Carlo rollouts (TD-Gammon / GNU Backgammon rollouts; points: see bgamd_env_rollout_outcomes_read) -----------------------
  * Plays T = trials games ("trials") from each of the P positions d_states28[P] / d_turn[P] (turn = side to move; d_turn NULL = PLAYER1)
  * with the greedy policy and reports how often PLAYER1 wins.  Trial i of position p is one game:
  *   - id and dice: j = (position_offset + p) * T + i; the dice of the trial's turn k (k = 0, 1, ...) are the TURN-stream dice of a lane with
@@ -296,6 +296,43 @@ int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_state
 /* The luck-adjusted results of the last bgamd_env_rollout, which must have had BGAMD_ROLLOUT_VR (else BGAMD_E_INVALID): d_vr_mean[P],
  * d_vr_stderr[P], d_trial_luck[P][T] = L_i (fp64, any may be NULL; P and T of that call).  Stream-ordered. */
 int bgamd_env_rollout_vr_read(bgamd_env *env, double *d_vr_mean, double *d_vr_stderr, double *d_trial_luck, void *stream);
+
+/* ---- gammons and backgammons: a finished game in points ------------------------------------------------------------------------------
+ * Backgammon is scored in points.  The reference knows wins only (over(), cppsrc/game.cpp:388-407), so the standard rules apply.  The
+ * winner is the side over() names (PLAYER1 is checked first: 15 off on both sides is PLAYER1's).  With the loser being the other side:
+ *   - single game (1 point): the loser has borne off at least one checker;
+ *   - backgammon (3 points): the loser has borne off none and has a checker on its bar or in the winner's home board (PLAYER1 won: a
+ *     PLAYER2 checker on points 19-24 or on PLAYER2's bar; PLAYER2 won: a PLAYER1 checker on points 1-6 or on PLAYER1's bar);
+ *   - gammon (2 points): everything else.
+ * Points are from PLAYER1's side: 0 = the game is not over, +1 / +2 / +3 = PLAYER1 won a single game / a gammon / a backgammon,
+ * -1 / -2 / -3 = PLAYER2 did.
+ * OUT OF SCOPE: games that are auto-reset inside a greedy step (BGAMD_AUTO_RESET, continuous self-play).  Their final boards are gone
+ * when the step returns; counting their gammons would mean changing the step's boundary launch.  The env's counters stay win / loss. */
+#define BGAMD_OUTCOME_BAD INT32_MIN
+/* points of each state from PLAYER1's side (0 = not over); a state with |count| > 15 gives BGAMD_OUTCOME_BAD (INT32_MIN).
+ * Stateless, stream-ordered, nothing synchronises.  n < 1 or a NULL pointer: BGAMD_E_INVALID. */
+int bgamd_outcomes(const int32_t *d_states28, int64_t n, int32_t *d_points, void *stream);
+/* the same for the CURRENT board of every lane of an env (d_points[n_games]): a frozen lane (finished without BGAMD_AUTO_RESET) keeps its
+ * final board, so this is the result of its game; a lane that is still playing, or was auto-reset, gives 0.  The env is not changed.
+ * Stream-ordered.  A NULL pointer: BGAMD_E_INVALID. */
+int bgamd_env_outcomes(bgamd_env *env, int32_t *d_points, void *stream);
+
+/* Outcomes of the last bgamd_env_rollout (any flags; BGAMD_E_INVALID before the first, or after one that failed; P and T of that call).
+ * Every trial that bgamd_env_rollout scores from a board -- a game that ended on its lane, a position that was already over, a rotated
+ * first turn that ended the game -- also records that board's points; a truncated trial (max_plies) records 0.  Any pointer may be NULL.
+ *   d_counts[P][6]     int64: trials that ended as PLAYER1 single, gammon, backgammon, PLAYER2 single, gammon, backgammon (truncated trials are
+ *                      in none of the six: the six sum to T - truncated[p]);
+ *   d_trial_points[P][T] int8: +-1, +-2, +-3, or 0 for a trial scored by the net;
+ *   equity of trial i, fp64, PLAYER1's cubeless money equity in points: (double) points_i for a finished trial; 2.0 * (double) x_i - 1.0 for a
+ *   truncated one (x_i = its fp32 net value: the net knows wins only, a truncated trial is credited no gammons);
+ *   d_equity[P] = (1/T) sum e_i;  d_equity_stderr[P] = sqrt(sum (e_i - mean)^2 / (T (T - 1))), 0 for T = 1.
+ * Reduced in the fixed order of the plain statistics: bit for bit the same for any `lanes`, from call to call and over position_offset
+ * splits.  Stream-ordered.  The plain outputs of bgamd_env_rollout, bgamd_env_rollout_info and bgamd_env_rollout_vr_read are what they
+ * were without this call.
+ * The luck adjustment stays a WIN-PROBABILITY quantity: vr_mean of bgamd_env_rollout_vr_read is not an equity, because the f and mean
+ * that make up a turn's luck come from a one-output net that estimates P(PLAYER1 wins) and knows nothing of gammons. */
+int bgamd_env_rollout_outcomes_read(bgamd_env *env, int64_t *d_counts, double *d_equity, double *d_equity_stderr,
+                                    int8_t *d_trial_points, void *stream);
 
 /* (slot 8 below counts the 32-row x 2-feature MFMA steps of the dense f32 net, or the W1 columns added by the
  * incremental one) */

@@ -7,7 +7,11 @@ live trial / all lane-steps, from bgamd_env_rollout_info).
 --vr: luck-adjusted rollouts (BGAMD_ROLLOUT_VR) instead, full (M = 0) and truncated (M = 7), --vr-trials rotated trials per position.  For
 each: the plain call and the VR call of the same trials, ms per call, the VR pass's virtual roots/s (21 per trial-turn over the time the
 VR call adds), the per-position variance ratio (stderr / vr_stderr)^2 (median, min, max, pooled) and effective trials/s (trials/s x the
-median ratio; 1 for the plain call)."""
+median ratio; 1 for the plain call).
+
+--outcomes: the same run with the games read in points after every call (bgamd_env_rollout_outcomes_read, inside the timed region):
+every record also carries the six shares (PLAYER1 single game / gammon / backgammon, PLAYER2 the same) over the finished trials of all
+positions and the mean equity of the positions in points."""
 import argparse
 import json
 import os
@@ -59,7 +63,10 @@ def main():
     ap.add_argument("--regions", type=int, default=3)
     ap.add_argument("--vr", action="store_true", help="luck-adjusted rollouts against plain ones")
     ap.add_argument("--vr-trials", type=int, default=2592)
+    ap.add_argument("--outcomes", action="store_true", help="also read gammons / backgammons and the equity in points")
     a = ap.parse_args()
+    if a.vr and a.outcomes:
+        ap.error("--outcomes reads the plain run's games; it is not combined with --vr")
     import backgammon_env as bg
     w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
     st, tu = _positions(bg, w, a.positions, 1)
@@ -78,7 +85,9 @@ def main():
         for _ in range(a.regions):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            r = env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes)
+            r = env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes, outcomes=a.outcomes)
+            if a.outcomes:
+                torch.cuda.synchronize()                           # (the read is stream-ordered after the call)
             ms.append((time.perf_counter() - t0) * 1e3)            # (the call synchronises)
         info = env.rollout_info()
         m = statistics.median(ms)
@@ -90,6 +99,12 @@ def main():
                "greedy_env_steps_per_s": round(greedy_sps), "ratio_to_greedy": round(turns / m * 1e3 / greedy_sps, 3),
                "idle_share": round(idle, 4), "env_steps": info[1], "turns_per_run": info[3], "mean_turns": round(turns / n_trials, 2),
                "truncated": int(r["truncated"].sum()), "regions_ms": [round(x, 2) for x in ms]}
+        if a.outcomes:
+            c = r["counts"].sum(0).cpu().numpy().astype(np.float64)
+            rec["outcome_shares"] = dict(zip(("p1_single", "p1_gammon", "p1_backgammon", "p2_single", "p2_gammon", "p2_backgammon"),
+                                             [round(float(x), 5) for x in c / max(c.sum(), 1.0)]))
+            rec["equity"] = round(float(r["equity"].mean()), 5)
+            rec["equity_stderr_median"] = round(float(r["equity_stderr"].median()), 5)
         print(json.dumps(rec), flush=True)
         out.append(rec)
     env.close()
