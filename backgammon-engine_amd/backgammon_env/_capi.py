@@ -116,6 +116,9 @@ SYMBOLS = [
     ("bgamd_td_slots", C.c_int, [_P, _P]),
     ("bgamd_td_time", C.c_int, [_P, C.c_int]),
     ("bgamd_td_times", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bgamd_td_fit_step", C.c_int, [_P, _P, _P, C.c_int64, C.c_double, _P, _P]),
+    ("bgamd_td_fit_step_allreduce", C.c_int, [_P, _P, _P, C.c_int64, C.c_double, _P]),
+    ("bgamd_td_fit_stats", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]
 
 

@@ -50,6 +50,19 @@ def stream_schedule(lengths, slots: int):
             n_steps, (k if games else 0))
 
 
+def fit_batches(n: int, epochs: int, batch: int, seed: int):
+    """The batches of DeviceTDLambdaLearner.fit: epoch e walks torch.randperm(n) of a CPU torch.Generator seeded with seed + e in
+    batches of `batch` indices, the last one short.  Yields (epoch, int64 index tensor on the CPU)."""
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    for e in range(int(epochs)):
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(int(seed) + e)
+        perm = torch.randperm(int(n), generator=gen)
+        for b0 in range(0, int(n), int(batch)):
+            yield e, perm[b0:b0 + int(batch)]
+
+
 class TDLambdaLearner:
     def __init__(self, weights_flat, device="cpu", alpha: float = 0.1, lam: float = 0.7, dtype=torch.float32):
         w = torch.as_tensor(weights_flat, dtype=dtype).flatten().to(device)
@@ -191,6 +204,33 @@ class TDLambdaLearner:
             self.theta.add_(held)
         return sq, cnt
 
+    def fit_step(self, X, targets, alpha=None, batch_scale: float = 1.0, group=None):
+        """One SUPERVISED step (DeviceTDLambdaLearner.fit_step, bgamd_td_fit_step) as a host closed form: X float [n, 198] encodings
+        (turn bit = side to move), targets float [n] = P(PLAYER1 wins) of every row (rollout means, search values).
+            δ_i = y_i - V(x_i), θ ← θ + Σ_i (α δ_i) ∇V(x_i)
+        -- replay's update of a terminal step with e = ∇ and a real-valued z: the squared-error gradient step.  A row whose target is
+        not finite adds nothing.  alpha defaults to learning_rate; batch_scale multiplies it, as in replay.
+        -> (Σ δ², rows that counted, rows skipped)."""
+        dev, dt = self.theta.device, self.theta.dtype
+        x = torch.as_tensor(X, device=dev).to(dt).reshape(-1, 198)
+        y = torch.as_tensor(targets, device=dev).to(dt).reshape(-1)
+        if y.numel() != x.shape[0]:
+            raise ValueError("one target per row")
+        a = float(self.learning_rate if alpha is None else alpha) * float(batch_scale)
+        ok = torch.isfinite(y)
+        W1, b1, W2, b2 = self._split(self.theta)
+        v, h = self.values(x)
+        delta = torch.where(ok, y - v, torch.zeros_like(v))
+        g = v * (1 - v) * ok.to(dt)
+        db1 = (g[:, None] * W2[None, :]) * h * (1 - h)
+        # α·δ is formed in float64 by the reference (python floats, train.py:147) before the fp32 multiply
+        coef = (a * delta.double()).to(dt)
+        upd = torch.cat([((coef[:, None] * db1).T @ x).reshape(-1), coef @ db1, (coef * g) @ h, (coef * g).sum().reshape(1)])
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)
+        self.theta.add_(upd)
+        return float((delta.double() ** 2).sum().item()), int(ok.sum().item()), int((~ok).sum().item())
+
     def state_dict(self):
         W1, b1, W2, b2 = TDLambdaLearner._split(self.theta.detach().cpu())
         return {"fc1.weight": W1.clone(), "fc1.bias": b1.clone(), "fc2.weight": W2.reshape(1, 128).clone(),
@@ -316,6 +356,74 @@ class DeviceTDLambdaLearner:
         ms, n, gs = C.c_double(), C.c_uint64(), C.c_uint64()
         self._capi.check(self._lib.bgamd_td_times(self._h, C.byref(ms), C.byref(n), C.byref(gs)), "td_times")
         return ms.value, n.value, gs.value
+
+    def fit_step(self, rows, targets, alpha=None, batch_scale: float = 1.0, group=None):
+        """One SUPERVISED step in a kernel of its own (csrc/bg_fit.h, bgamd_td_fit_step): rows int32 [n, 8] packed 32-byte rows
+        (pack_rows; the turn bit is the side to move), targets float32 [n] = P(PLAYER1 wins) of every row -- rollout means
+        (VecGame.rollout), search values.  θ ← θ + Σ_i fp32(α δ_i) ∇V(x_i) with δ_i = y_i - V(x_i): the squared-error gradient step, the
+        TD update of a terminal step with a real-valued target and no trace.  A row whose target is not finite adds nothing and is
+        counted as skipped (fit_stats).  alpha defaults to learning_rate, batch_scale multiplies it.  n is not bounded by max_games;
+        n = 0 is a rank without rows.  Call it between replays.  Distributed: as replay_rows -- the library's own all-reduce where the
+        learner has a communicator (init_collective), torch.distributed otherwise.  Enqueues only: no host wait."""
+        C, lib, chk = self._C, self._lib, self._capi.check
+        rows = torch.as_tensor(rows, device=self.device).to(torch.int32).reshape(-1, 8).contiguous()
+        y = torch.as_tensor(targets, device=self.device).to(torch.float32).reshape(-1).contiguous()
+        n = int(rows.shape[0])
+        if int(y.numel()) != n:
+            raise ValueError("one target per row")
+        a = float(self.learning_rate if alpha is None else alpha) * float(batch_scale)
+        pr, py = (self._p(rows), self._p(y)) if n else (None, None)
+        distributed = self._distributed(group)
+        if not distributed:
+            chk(lib.bgamd_td_fit_step(self._h, pr, py, n, a, None, self._s()), "td_fit_step")
+        elif self._in_library(True):
+            chk(lib.bgamd_td_fit_step_allreduce(self._h, pr, py, n, a, self._s()), "td_fit_step_allreduce")
+        else:
+            upd = torch.empty(25601, dtype=torch.float32, device=self.device)
+            chk(lib.bgamd_td_fit_step(self._h, pr, py, n, a, self._p(upd), self._s()), "td_fit_step")
+            dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)
+            chk(lib.bgamd_td_apply(self._h, self._p(upd), self._s()), "td_apply")
+        # (rows and y may die here: the kernels read them later, but torch's caching allocator hands a freed block only to work queued
+        #  behind them on this same stream)
+
+    def fit_stats(self):
+        """(Σ δ², rows that counted, rows skipped) of the fit steps since the learner was made or since the last call (waits for the
+        stream of the last fit step)."""
+        C = self._C
+        sq, cnt, sk = C.c_double(), C.c_int64(), C.c_int64()
+        self._capi.check(self._lib.bgamd_td_fit_stats(self._h, C.byref(sq), C.byref(cnt), C.byref(sk)), "td_fit_stats")
+        return float(sq.value), int(cnt.value), int(sk.value)
+
+    def _pack_rows(self, states28, turn):
+        from . import pack_rows
+        return pack_rows(states28, turn, device=self.device)
+
+    def fit(self, states28, turn, targets, epochs: int = 1, batch: int = 4096, seed: int = 0, alpha=None, batch_scale=None):
+        """Fits the net to (position, target) pairs: states28 [n, 28] reference-layout states, turn [n] the side to move, targets [n]
+        = P(PLAYER1 wins).  The rows are packed once; epoch e walks the permutation fit_batches draws from a CPU torch.Generator seeded
+        with seed + e, in batches of `batch` rows, the last one short; every batch is one fit_step.  batch_scale defaults to
+        24 / batch (the convention TDLambdaLearner.replay documents: the update of a reference-sized round).
+        -> the mean squared error of every epoch, [Σ δ² / rows that counted], as the steps saw it (fit_stats)."""
+        rows = self._pack_rows(states28, turn).reshape(-1, 8)
+        y = torch.as_tensor(targets, dtype=torch.float32).to(rows.device).reshape(-1)
+        n = int(rows.shape[0])
+        if int(y.numel()) != n:
+            raise ValueError("one target per position")
+        if batch_scale is None:
+            batch_scale = 24.0 / int(batch)
+        self.fit_stats()
+        mse, epoch = [], 0
+        for e, idx in fit_batches(n, epochs, batch, seed):
+            if e != epoch:
+                sq, cnt, _ = self.fit_stats()
+                mse.append(sq / max(cnt, 1))
+                epoch = e
+            idx = idx.to(rows.device)
+            self.fit_step(rows[idx], y[idx], alpha=alpha, batch_scale=batch_scale)
+        if n and epochs > 0:
+            sq, cnt, _ = self.fit_stats()
+            mse.append(sq / max(cnt, 1))
+        return mse
 
     def replay_rows(self, rows, lengths, p1_won, group=None, batch_scale: float = 1.0, split_apply: bool = False,
                     sub_round: int = 0, slots: int = 0):

@@ -37,6 +37,7 @@
 #include "bg_eval_dense16.h"
 #endif
 #include "bg_learner.h"
+#include "bg_fit.h"
 #include "bg_schedule.h"
 #include "bg_movegen.h"
 #include "bg_staged.h"
@@ -2560,6 +2561,14 @@ struct bgamd_td {
     size_t ev_used = 0;
     double trace_ms = 0;
     uint64_t trace_launches = 0, trace_game_steps = 0;
+    // the supervised step (bgamd_td_fit_step, bg_fit.h)
+    long long fit_chunk = FIT_CHUNK_ROWS;   // rows per kernel pair (BGAMD_FIT_CHUNK, a multiple of 32)
+    int fit_groups = TD_MAX_GROUPS;         // most workgroups of a launch (BGAMD_FIT_GROUPS, 1 .. 256: tests reach several tiles per workgroup with few rows)
+    float *fit_run = nullptr;               // [TD_LD] the update summed over the chunks so far, internal order
+    double *fit_part_sq = nullptr;          // [TD_MAX_GROUPS] per workgroup: Σ δ²
+    long long *fit_part_cnt = nullptr;      // [TD_MAX_GROUPS][2] rows that counted | rows skipped
+    double *fit_stat = nullptr;             // [4] x 8 B: Σ δ² (double) | rows | skipped (int64) since create / the last bgamd_td_fit_stats
+    hipStream_t fit_stream = nullptr;       // the stream of the last fit step: what bgamd_td_fit_stats waits for
 };
 
 namespace {
@@ -2621,7 +2630,21 @@ int bgamd_td_create(bgamd_td **out, int64_t max_games, int device)
     TDALLOC(v.wl3, 3 * EVAL16_W_BYTES);
     TDALLOC(v.lut, EVAL16_LUT_BYTES);
     TDALLOC(v.hid, (size_t)max_games * 2 * N_HID * 4);
+    TDALLOC(td->fit_run, TD_LD * 4);
+    TDALLOC(td->fit_part_sq, TD_MAX_GROUPS * 8);
+    TDALLOC(td->fit_part_cnt, TD_MAX_GROUPS * 2 * 8);
+    TDALLOC(td->fit_stat, 4 * 8);
 #undef TDALLOC
+    HIPCHK(hipMemset(td->fit_stat, 0, 4 * 8));
+    if (getenv("BGAMD_FIT_CHUNK")) {
+        long long c = atoll(getenv("BGAMD_FIT_CHUNK"));
+        c = c < FIT_TILE ? FIT_TILE : (c > (1ll << 22) ? (1ll << 22) : c);
+        td->fit_chunk = (c + FIT_TILE - 1) / FIT_TILE * FIT_TILE;
+    }
+    if (getenv("BGAMD_FIT_GROUPS")) {
+        const int g = atoi(getenv("BGAMD_FIT_GROUPS"));
+        td->fit_groups = g < 1 ? 1 : (g > TD_MAX_GROUPS ? TD_MAX_GROUPS : g);
+    }
     {
         uint32_t lut[32];
         make_count_lut(lut);
@@ -2671,6 +2694,8 @@ int bgamd_td_destroy(bgamd_td *td)
     if (td->d_upd) hipFree(td->d_upd);
     for (int k = 0; k < 2; ++k) { if (td->theta2[k]) hipFree(td->theta2[k]); if (td->wl3_2[k]) hipFree(td->wl3_2[k]); }
     if (td->partial2) hipFree(td->partial2);
+    void *fit_ptrs[] = {td->fit_run, td->fit_part_sq, td->fit_part_cnt, td->fit_stat};
+    for (void *p : fit_ptrs) if (p) hipFree(p);
     delete td;
     return BGAMD_OK;
 }
@@ -2913,6 +2938,60 @@ int bgamd_td_apply(bgamd_td *td, const float *d_update, void *stream)
     if (!td->has_weights) return BGAMD_E_NOWEIGHTS;
     hipLaunchKernelGGL(td_apply_kernel, grid1(TD_P, 256), dim3(256), 0, (hipStream_t)stream, td->v, d_update, 0);
     HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+// The supervised step (bg_fit.h): rows and targets -> update = Σ_i fp32(alpha · (y_i - V(x_i))) ∇V(x_i), in chunks of td->fit_chunk rows;
+// every chunk is fit_step_kernel + fit_reduce_kernel, the last reduce hands the update out or applies it.  Stream-ordered, no host wait;
+// touches nothing of a replay's state but the partial sums, which are free between replays.
+int bgamd_td_fit_step(bgamd_td *td, const void *d_rows, const float *d_target, int64_t n, double alpha, float *d_update, void *stream)
+{
+    if (!td || n < 0 || (n > 0 && (!d_rows || !d_target))) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(td->device));
+    if (!td->has_weights) return BGAMD_E_NOWEIGHTS;
+    hipStream_t s = (hipStream_t)stream;
+    td->fit_stream = s;
+    if (n == 0) {                        // a rank without rows still hands a defined buffer to the collective
+        if (d_update) HIPCHK(hipMemsetAsync(d_update, 0, (size_t)TD_P * 4, s));
+        return BGAMD_OK;
+    }
+    const long long chunk = td->fit_chunk;
+    const long long n_chunks = (n + chunk - 1) / chunk;
+    for (long long c = 0; c < n_chunks; ++c) {
+        const long long r0 = c * chunk;
+        const long long m = n - r0 < chunk ? n - r0 : chunk;
+        FitView f{};
+        f.rows = (const uint4 *)d_rows + 2 * r0;
+        f.target = d_target + r0;
+        f.m = m;
+        f.tiles = (int)((m + FIT_TILE - 1) / FIT_TILE);
+        f.theta = td->v.theta; f.w1t = td->v.w1t;
+        f.partial = td->v.partial;
+        f.part_sq = td->fit_part_sq; f.part_cnt = td->fit_part_cnt;
+        const int groups = f.tiles < td->fit_groups ? f.tiles : td->fit_groups;
+        hipLaunchKernelGGL(fit_step_kernel, dim3(groups), dim3(FIT_THREADS), 0, s, f, alpha);
+        const int last = c + 1 == n_chunks ? 1 : 0;
+        hipLaunchKernelGGL(fit_reduce_kernel, grid1(TD_P, 64), dim3(256), 0, s, td->v, groups, td->fit_run, c == 0 ? 1 : 0, last, d_update,
+                           d_update ? 0 : 1, (const double *)td->fit_part_sq, (const long long *)td->fit_part_cnt, td->fit_stat,
+                           (long long *)(td->fit_stat + 1));
+    }
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_td_fit_stats(bgamd_td *td, double *h_sq_sum, int64_t *h_rows, int64_t *h_skipped)
+{
+    if (!td) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(td->device));
+    double h[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h, td->fit_stat, sizeof(h), hipMemcpyDeviceToHost, td->fit_stream));
+    HIPCHK(hipMemsetAsync(td->fit_stat, 0, sizeof(h), td->fit_stream));
+    HIPCHK(hipStreamSynchronize(td->fit_stream));
+    long long cnt[2];
+    memcpy(cnt, &h[1], sizeof(cnt));
+    if (h_sq_sum) *h_sq_sum = h[0];
+    if (h_rows) *h_rows = cnt[0];
+    if (h_skipped) *h_skipped = cnt[1];
     return BGAMD_OK;
 }
 
@@ -3224,6 +3303,20 @@ int bgamd_td_step_allreduce(bgamd_td *td, int64_t t, int64_t n_active, double al
         HIPCHK(hipMemsetAsync(td->d_upd, 0, (size_t)TD_P * 4, s));
         td->last_stream = s;
     }
+    RcclApi *api = rccl_api();
+    RCCLCHK(api, api->AllReduce(td->d_upd, td->d_upd, (size_t)TD_P, ncclFloat32, ncclSum, (ncclComm_t)td->comm, s));
+    hipLaunchKernelGGL(td_apply_kernel, grid1(TD_P, 256), dim3(256), 0, s, td->v, (const float *)td->d_upd, 0);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+// the supervised step of a multi-rank fit: fit step with the update handed out -> ncclAllReduce -> apply, as bgamd_td_step_allreduce
+int bgamd_td_fit_step_allreduce(bgamd_td *td, const void *d_rows, const float *d_target, int64_t n, double alpha, void *stream)
+{
+    if (!td || !td->comm || !td->d_upd) return BGAMD_E_INVALID;
+    const int rc = bgamd_td_fit_step(td, d_rows, d_target, n, alpha, td->d_upd, stream);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
     RcclApi *api = rccl_api();
     RCCLCHK(api, api->AllReduce(td->d_upd, td->d_upd, (size_t)TD_P, ncclFloat32, ncclSum, (ncclComm_t)td->comm, s));
     hipLaunchKernelGGL(td_apply_kernel, grid1(TD_P, 256), dim3(256), 0, s, td->v, (const float *)td->d_upd, 0);

@@ -564,6 +564,29 @@ int bgamd_td_slots(bgamd_td *td, int32_t *h_out);
 int bgamd_td_time(bgamd_td *td, int enable);
 int bgamd_td_times(bgamd_td *td, double *h_trace_ms, uint64_t *h_launches, uint64_t *h_game_steps);
 
+/* ---- supervised step: fit the value net to real-valued targets (rollout means, search values) --------------------------------
+ * d_rows = n rows of 32 B (bgamd_pack_rows; the turn bit is the side to move), d_target = n floats, y_i = P(PLAYER1 wins) of row i.
+ *   update = Σ_i fp32(alpha · δ_i) ∇V(x_i), δ_i = y_i - V(x_i) in fp32, alpha·δ formed in float64 (train.py:147)
+ * -- bgamd_td_step's update of a terminal step with e = ∇ and a real-valued z: the squared-error gradient step of the reference's own
+ * learner.  A row whose target is not finite adds nothing and is counted as skipped.  d_update == NULL: the update is applied to the
+ * weights, and every copy of them the TD kernels read is refreshed as after a TD step.  Otherwise it is written to d_update[25601] and
+ * NOT applied: the caller all-reduces it and calls bgamd_td_apply, as with bgamd_td_step.  n = 0 is allowed (d_rows and d_target may
+ * be NULL): a zero update, so that a rank without rows joins the collective.  n is not bounded by max_games: the rows are walked in
+ * chunks of 65 536 (BGAMD_FIT_CHUNK at bgamd_td_create: another multiple of 32).  Stream-ordered, no host wait, no bgamd_td_begin
+ * needed.  Deterministic: the same rows, targets, weights and alpha give the same bits (csrc/bg_fit.h states the order of the sums).
+ * Call it BETWEEN replays: it leaves traces, slots, queue cursors, bgamd_td_stats and the column counters as they are, but uses the
+ * replay's buffer of partial sums, so it must not be enqueued between the steps of a replay with a delayed update pending
+ * (bgamd_td_set_delay) or on another stream than a replay still in flight.
+ * fit_stats: Σ δ², the rows that counted and the rows skipped since bgamd_td_create or the last call of it; waits for the stream of
+ * the last fit step, which must still exist (before any fit step: the null stream).  BGAMD_FIT_CHUNK and BGAMD_FIT_GROUPS (most
+ * workgroups per launch, 1 .. 256) are read at bgamd_td_create: test hooks that reach several chunks and several tiles per workgroup
+ * with few rows; both change the order of the sums (csrc/bg_fit.h), not what is summed. */
+int bgamd_td_fit_step(bgamd_td *td, const void *d_rows, const float *d_target, int64_t n, double alpha, float *d_update, void *stream);
+int bgamd_td_fit_stats(bgamd_td *td, double *h_sq_sum, int64_t *h_rows, int64_t *h_skipped);
+/* ... with the library's own collective (bgamd_td_comm_init): fit step -> ncclAllReduce(sum, in place) -> bgamd_td_apply, three
+ * enqueues on `stream`; n = 0: the rank adds nothing but joins. */
+int bgamd_td_fit_step_allreduce(bgamd_td *td, const void *d_rows, const float *d_target, int64_t n, double alpha, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
