@@ -13,6 +13,7 @@
 // 32-lane butterfly), + b2, sigmoid -> one fp32 value per row.
 #pragma once
 #include "bg_board.h"
+#include "bg_td_plan.h"                  // ROOT3_THREADS: the learner's step plan sizes the trajectory pass's grid by it
 
 namespace bg {
 
@@ -848,7 +849,6 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_rows_bf16_kernel(
 // accumulation -- fp32-grade results at 3/16 of the fp32 MFMA's cost.  Used for the one dense pass per GAME
 // (root positions); output = -log2(e) (W1 x + b1), what eval_rows_delta_kernel starts from.
 // The three weight planes (160 KB) do not fit LDS together: K is staged in two phases (7 + 6 K-steps).
-constexpr int ROOT3_THREADS = 512;
 #ifndef BG_ROOT3_PHASE_STEPS
 #define BG_ROOT3_PHASE_STEPS 7
 #endif

@@ -46,12 +46,10 @@
 
 namespace bg {
 
-constexpr int FIT_TILE = 32;                 // rows per tile = the M of the forward product, the K of the gradient product
 constexpr int FIT_THREADS = 256;             // four waves: wave c owns hidden units 32 c .. 32 c + 31
 constexpr int FIT_FT = 7;                    // feature tiles of 32: 198 -> 224 columns, the last 26 zero
 constexpr int FIT_XLD = 225;                 // row stride of sX (odd: the forward's A operand, one row per lane, meets no bank twice)
 constexpr int FIT_HLD = N_HID + 1;
-constexpr long long FIT_CHUNK_ROWS = 65536;  // 256 workgroups x 8 tiles
 
 struct FitView {
     const uint4 *rows;                       // [m] x 2 uint4: the chunk's rows

@@ -44,24 +44,16 @@
 #pragma once
 #include "bg_board.h"
 #include "bg_eval.h"
+#include "bg_td_plan.h"                  // TD_LD, TD_CHUNK, TD_MAX_GROUPS, TD_FUSED_GAMES, TD_DELAY_SLICES: shared with the host's step plan
 
 namespace bg {
 
 constexpr int TD_P = 25601;              // W1[128][198] | b1[128] | W2[128] | b2
-constexpr int TD_LD = 25664;             // trace row stride in floats (multiple of 64)
 constexpr int TD_OFF_B1 = 25344, TD_OFF_W2 = 25472, TD_OFF_B2 = 25600;
 // factor row of one game: the 32-byte row of s_t (8 words: the trace pass decodes x_j from it) | db1[128] | g·h[128] | g | pad
 constexpr int TD_F_ROW = 0, TD_F_DB1 = 8, TD_F_GH = 136, TD_F_G = 264, TD_FLD = 272;
 constexpr int TD_TRACE_THREADS = 256;
 constexpr int TD_SLICES = (TD_LD / 4 + TD_TRACE_THREADS - 1) / TD_TRACE_THREADS;   // 26
-#ifndef BG_TD_CHUNK
-#define BG_TD_CHUNK 8
-#endif
-constexpr int TD_CHUNK = BG_TD_CHUNK;    // games staged in LDS at a time by the trace kernel
-#ifndef BG_TD_MAX_GROUPS
-#define BG_TD_MAX_GROUPS 256
-#endif
-constexpr int TD_MAX_GROUPS = BG_TD_MAX_GROUPS;
 constexpr int TD_MASK_WORDS = 8;         // 198 feature bits in 7 words, padded to 32 B per game
 // INTERNAL order of a trace row / partial-sum row (the parameter order of theta is fc1.weight[n][j] | b1 | W2 | b2):
 //   [j * 128 + n] = W1[n][j] for j < 198 (feature-major: a column of W1 is 512 contiguous bytes), then b1, W2, b2 at the
@@ -478,7 +470,6 @@ __global__ __launch_bounds__(256) void td_epilogue_wave_kernel(TdView v, long lo
 // 16 slots x {s_t, s_{t+1}}, wave c = hidden units 32 c .. 32 c + 31, weight planes straight from the L2) with the epilogue on the
 // accumulators -- σ, the W2 dot through LDS (32 rows x 128 products, 8 threads per row), δ, g, coef, the factor rows, the masks, the
 // slot's next game: no `hid` round trip, no second launch (5.9 us + a kernel boundary of the ~49 us step at 2 048 slots).
-constexpr int TD_FUSED_GAMES = 16;
 __global__ __launch_bounds__(ROOT3D_THREADS) void td_forward_mfma_kernel(TdView v, long long t, long long n_active, double alpha)
 {
     constexpr int G = TD_FUSED_GAMES;
@@ -1064,8 +1055,6 @@ __global__ __launch_bounds__(TD_WIDE_THREADS) void td_trace_pipe_kernel(TdView v
 // waves 0-3 run the forward pass, 128 parameters per workgroup, into the OTHER weight buffer: this launch reads theta / wl3 / the partial sums
 // of step t - 1 and writes th_next / wl3_next / its own partial sums, nobody reads what anybody writes.  A documented deviation (one game no
 // longer reproduces the reference's update step for step): opt-in.
-constexpr int TD_DELAY_SLICE = 128;                                              // parameters (internal order) per workgroup and slice: 4 cache lines
-constexpr int TD_DELAY_SLICES = (TD_LD + TD_DELAY_SLICE - 1) / TD_DELAY_SLICE;   // 201 (the last one reads 64 floats past a row: the next row, or the zeroed tail)
 
 // threads j = 0 .. 255 of a workgroup: float4 f = j & 31 of slice `slice`, partial rows r, r + 8, ... -> red[r][f]; call td_delay_finish after a barrier
 __device__ __forceinline__ void td_delay_gather(const float *__restrict__ part_prev, int n_prev, int slice, int j, td_f32x4 (*red)[32])

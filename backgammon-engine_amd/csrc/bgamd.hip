@@ -2529,19 +2529,7 @@ struct bgamd_td {
     TdView v{};
     bool has_weights = false, begun = false;
     int n_cu = 256;
-    long long mfma_min = 24576;            // running games from which the forward pass uses the LDS-staged matrix-pipe kernel (BGAMD_TD_MFMA_MIN;
-                                           //   measured equal to the direct one from there up, slower below: 153 vs 132 ms per round at 3 072 slots)
-    bool fused = true;                     // ... with its epilogue in the same launch (BGAMD_TD_FUSED=0: two launches)
-    long long direct_min = 512;            // ... from which it runs as one workgroup per 32-row tile, weights from the L2 (BGAMD_TD_DIRECT_MIN)
-    long long nt_min = 8192;               // ... from which the whole-row trace pass uses nontemporal loads / stores (BGAMD_TD_NT_MIN)
-    long long wide_min = 8192;             // running games from which the trace pass uses the whole-row workgroups (BGAMD_TD_WIDE_MIN)
-    bool pipe = true;                      // mid-sized steps: the software-pipelined whole-row pass (BGAMD_TD_PIPE=0: td_trace_wide_kernel)
-    bool fuse_step = true;                 // ... with the forward pass of the same slots in the same launch (BGAMD_TD_FUSE_STEP=0: two launches)
-    long long fuse_min = 512;              // ... from this many running slots (measured: 512 slots 27 vs 31 us per step, 256 slots 28 vs 26) up to 16 per CU (BGAMD_TD_FUSE_MIN)
-    int fuse_g = 0;                        // ... slots per workgroup of that launch: 0 = by step size (BGAMD_TD_FUSE_G = 1, 2, 4, 8, 16)
-    long long slice_ng = 0;                // BGAMD_TD_NG: games per group of the slice kernel at mid-sized steps (0: as many groups as allowed)
-    bool no_wide_even = false;             // BGAMD_TD_NO_WIDE_EVEN=1: mid-sized steps never take the whole-row kernels
-    bool lazy = true;                      // lazily scaled traces (bg_learner.h); BGAMD_TD_LAZY=0: e <- λ e + ∇ every step
+    TdTuning tune;                         // the thresholds and switches of the step's dispatch (bg_td_plan.h), read at create
     double scale = 1.0;                    // c: stored trace = e / c, the same for every game of the replay
     bool stream_mode = false;              // bgamd_td_begin_stream: slots take game after game, steps are not bounded by the log length
     hipStream_t last_stream = nullptr;     // the stream the replay at hand is issued on: what the readers below wait for (a learner replaying on
@@ -2562,8 +2550,6 @@ struct bgamd_td {
     double trace_ms = 0;
     uint64_t trace_launches = 0, trace_game_steps = 0;
     // the supervised step (bgamd_td_fit_step, bg_fit.h)
-    long long fit_chunk = FIT_CHUNK_ROWS;   // rows per kernel pair (BGAMD_FIT_CHUNK, a multiple of 32)
-    int fit_groups = TD_MAX_GROUPS;         // most workgroups of a launch (BGAMD_FIT_GROUPS, 1 .. 256: tests reach several tiles per workgroup with few rows)
     float *fit_run = nullptr;               // [TD_LD] the update summed over the chunks so far, internal order
     double *fit_part_sq = nullptr;          // [TD_MAX_GROUPS] per workgroup: Σ δ²
     long long *fit_part_cnt = nullptr;      // [TD_MAX_GROUPS][2] rows that counted | rows skipped
@@ -2577,6 +2563,56 @@ hipError_t td_read(bgamd_td *td, void *dst, const void *src, size_t bytes)
 {
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, td->last_stream);
     return e != hipSuccess ? e : hipStreamSynchronize(td->last_stream);
+}
+// The learner's device buffers, the ONE list of them: bgamd_td_create allocates those of TD_AT_CREATE, the delayed replay and
+// bgamd_td_comm_init theirs at first use, bgamd_td_destroy frees whatever of the list is allocated.  A new buffer needs its member
+// AND its line here: one left out is never allocated and stays null, which its first kernel trips over at once.
+enum TdWhen { TD_AT_CREATE, TD_AT_DELAY, TD_AT_COMM };
+struct TdBuf { void **ptr; size_t bytes; const char *name; TdWhen when; };
+std::vector<TdBuf> td_buffers(bgamd_td *td)
+{
+    TdView &v = td->v;
+    const size_t n = (size_t)td->max_games;
+    const size_t partial_bytes = ((size_t)TD_MAX_GROUPS * TD_LD + 64) * 4;     // + a zeroed line: the dummy source of the pipelined trace pass
+#define TDBUF(ptr, bytes, when) TdBuf{(void **)&(ptr), (size_t)(bytes), #ptr, when}
+    return {
+        TDBUF(v.theta, TD_LD * 4, TD_AT_CREATE),                  TDBUF(v.w1t, N_IN * N_HID * 4, TD_AT_CREATE),
+        TDBUF(v.e, n * TD_LD * 4, TD_AT_CREATE),                  TDBUF(v.fac, n * TD_FLD * 4, TD_AT_CREATE),
+        TDBUF(v.coef, n * 4, TD_AT_CREATE),                       TDBUF(v.sq, n * 8, TD_AT_CREATE),
+        TDBUF(v.gmeta, n * 16, TD_AT_CREATE),                     TDBUF(v.partial, partial_bytes, TD_AT_CREATE),
+        TDBUF(v.amask, n * TD_MASK_WORDS * 4, TD_AT_CREATE),      TDBUF(v.anew, n * TD_MASK_WORDS * 4, TD_AT_CREATE),
+        TDBUF(v.act_cols, n * 4, TD_AT_CREATE),                   TDBUF(v.wr_cols, n * 4, TD_AT_CREATE),
+        TDBUF(v.nupd, n * 4, TD_AT_CREATE),                       TDBUF(v.qcur, n * 4, TD_AT_CREATE),
+        TDBUF(v.wl3, 3 * EVAL16_W_BYTES, TD_AT_CREATE),           TDBUF(v.lut, EVAL16_LUT_BYTES, TD_AT_CREATE),
+        TDBUF(v.hid, n * 2 * N_HID * 4, TD_AT_CREATE),            TDBUF(td->fit_run, TD_LD * 4, TD_AT_CREATE),
+        TDBUF(td->fit_part_sq, TD_MAX_GROUPS * 8, TD_AT_CREATE),  TDBUF(td->fit_part_cnt, TD_MAX_GROUPS * 2 * 8, TD_AT_CREATE),
+        TDBUF(td->fit_stat, 4 * 8, TD_AT_CREATE),
+        TDBUF(td->theta2[0], TD_LD * 4, TD_AT_DELAY),             TDBUF(td->wl3_2[0], 3 * EVAL16_W_BYTES, TD_AT_DELAY),
+        TDBUF(td->theta2[1], TD_LD * 4, TD_AT_DELAY),             TDBUF(td->wl3_2[1], 3 * EVAL16_W_BYTES, TD_AT_DELAY),
+        TDBUF(td->partial2, partial_bytes, TD_AT_DELAY),
+        TDBUF(td->d_upd, TD_P * 4, TD_AT_COMM),
+    };
+#undef TDBUF
+}
+// allocate the buffers of `when` that are not there yet; the error text names the one that failed
+int td_alloc(bgamd_td *td, TdWhen when)
+{
+    for (const TdBuf &b : td_buffers(td)) {
+        if (b.when != when || *b.ptr) continue;
+        const hipError_t e = hipMalloc(b.ptr, b.bytes);
+        if (e != hipSuccess) { g_hip_err = std::string("hipMalloc(") + b.name + "): " + hipGetErrorString(e); return BGAMD_E_HIP; }
+    }
+    return BGAMD_OK;
+}
+// Σ over the slots of one of their 32-bit counters (nupd, act_cols, wr_cols)
+int td_sum_slots(bgamd_td *td, const unsigned int *d_counter, uint64_t *h_sum)
+{
+    std::vector<unsigned int> c((size_t)td->v.n_games);
+    if (!c.empty()) HIPCHK(td_read(td, c.data(), d_counter, c.size() * 4));
+    uint64_t tot = 0;
+    for (unsigned int x : c) tot += x;
+    *h_sum = tot;
+    return BGAMD_OK;
 }
 int td_flush(bgamd_td *td)
 {
@@ -2603,48 +2639,15 @@ int bgamd_td_create(bgamd_td **out, int64_t max_games, int device)
     td->device = device;
     td->max_games = max_games;
     TdView &v = td->v;
-    auto fail = [&](int rc) { bgamd_td_destroy(td); return rc; };
-#define TDALLOC(ptr, bytes)                                                         \
-    do {                                                                            \
-        hipError_t _e = hipMalloc((void **)&(ptr), (size_t)(bytes));                \
-        if (_e != hipSuccess) {                                                     \
-            g_hip_err = std::string("hipMalloc(" #ptr "): ") + hipGetErrorString(_e); \
-            return fail(BGAMD_E_HIP);                                               \
-        }                                                                           \
-    } while (0)
-    TDALLOC(v.theta, TD_LD * 4);
-    TDALLOC(v.w1t, N_IN * N_HID * 4);
-    TDALLOC(v.e, (size_t)max_games * TD_LD * 4);
-    TDALLOC(v.fac, (size_t)max_games * TD_FLD * 4);
-    TDALLOC(v.coef, (size_t)max_games * 4);
-    TDALLOC(v.sq, (size_t)max_games * 8);
-    TDALLOC(v.gmeta, (size_t)max_games * 16);
-    TDALLOC(v.partial, ((size_t)TD_MAX_GROUPS * TD_LD + 64) * 4);          // + a zeroed line: the dummy source of the pipelined trace pass
+    if (td_alloc(td, TD_AT_CREATE)) { bgamd_td_destroy(td); return BGAMD_E_HIP; }
     HIPCHK(hipMemset(v.partial + (size_t)TD_MAX_GROUPS * TD_LD, 0, 64 * 4));
-    TDALLOC(v.amask, (size_t)max_games * TD_MASK_WORDS * 4);
-    TDALLOC(v.anew, (size_t)max_games * TD_MASK_WORDS * 4);
-    TDALLOC(v.act_cols, (size_t)max_games * 4);
-    TDALLOC(v.wr_cols, (size_t)max_games * 4);
-    TDALLOC(v.nupd, (size_t)max_games * 4);
-    TDALLOC(v.qcur, (size_t)max_games * 4);
-    TDALLOC(v.wl3, 3 * EVAL16_W_BYTES);
-    TDALLOC(v.lut, EVAL16_LUT_BYTES);
-    TDALLOC(v.hid, (size_t)max_games * 2 * N_HID * 4);
-    TDALLOC(td->fit_run, TD_LD * 4);
-    TDALLOC(td->fit_part_sq, TD_MAX_GROUPS * 8);
-    TDALLOC(td->fit_part_cnt, TD_MAX_GROUPS * 2 * 8);
-    TDALLOC(td->fit_stat, 4 * 8);
-#undef TDALLOC
     HIPCHK(hipMemset(td->fit_stat, 0, 4 * 8));
-    if (getenv("BGAMD_FIT_CHUNK")) {
-        long long c = atoll(getenv("BGAMD_FIT_CHUNK"));
-        c = c < FIT_TILE ? FIT_TILE : (c > (1ll << 22) ? (1ll << 22) : c);
-        td->fit_chunk = (c + FIT_TILE - 1) / FIT_TILE * FIT_TILE;
-    }
-    if (getenv("BGAMD_FIT_GROUPS")) {
-        const int g = atoi(getenv("BGAMD_FIT_GROUPS"));
-        td->fit_groups = g < 1 ? 1 : (g > TD_MAX_GROUPS ? TD_MAX_GROUPS : g);
-    }
+#ifdef BGAMD_EXPERIMENTAL
+    td->tune = td_tuning_from_env(getenv, true);
+#else
+    td->tune = td_tuning_from_env(getenv, false);
+#endif
+    v.dense = (int)td->tune.dense;
     {
         uint32_t lut[32];
         make_count_lut(lut);
@@ -2654,25 +2657,7 @@ int bgamd_td_create(bgamd_td **out, int64_t max_games, int device)
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
         td->n_cu = prop.multiProcessorCount;
-        td->mfma_min = getenv("BGAMD_TD_MFMA_MIN") ? atoll(getenv("BGAMD_TD_MFMA_MIN")) : 24576;
     }
-    v.dense = getenv("BGAMD_TD_DENSE") != nullptr ? 1 : 0;
-    if (getenv("BGAMD_TD_WIDE_MIN")) td->wide_min = atoll(getenv("BGAMD_TD_WIDE_MIN"));
-    if (getenv("BGAMD_TD_NT_MIN")) td->nt_min = atoll(getenv("BGAMD_TD_NT_MIN"));
-    td->pipe = !(getenv("BGAMD_TD_PIPE") && atoi(getenv("BGAMD_TD_PIPE")) == 0);
-    if (getenv("BGAMD_TD_NG")) td->slice_ng = atoll(getenv("BGAMD_TD_NG"));
-    td->fuse_step = !(getenv("BGAMD_TD_FUSE_STEP") && atoi(getenv("BGAMD_TD_FUSE_STEP")) == 0);
-    if (getenv("BGAMD_TD_FUSE_MIN")) td->fuse_min = atoll(getenv("BGAMD_TD_FUSE_MIN"));
-    if (getenv("BGAMD_TD_FUSE_G")) {
-        const int g = atoi(getenv("BGAMD_TD_FUSE_G"));
-        td->fuse_g = (g == 1 || g == 2 || g == 4 || g == 8 || g == 16) ? g : 0;
-    }
-    td->no_wide_even = getenv("BGAMD_TD_NO_WIDE_EVEN") != nullptr && atoi(getenv("BGAMD_TD_NO_WIDE_EVEN")) != 0;
-#ifdef BGAMD_EXPERIMENTAL
-    td->fused = !(getenv("BGAMD_TD_FUSED") && atoi(getenv("BGAMD_TD_FUSED")) == 0);      // (the unfused matrix-pipe forward: experimental build only)
-#endif
-    if (getenv("BGAMD_TD_DIRECT_MIN")) td->direct_min = atoll(getenv("BGAMD_TD_DIRECT_MIN"));
-    td->lazy = !(getenv("BGAMD_TD_LAZY") && atoi(getenv("BGAMD_TD_LAZY")) == 0);
     HIPCHK(hipMemset(v.act_cols, 0, (size_t)max_games * 4));
     HIPCHK(hipMemset(v.wr_cols, 0, (size_t)max_games * 4));
     HIPCHK(hipMemset(v.theta, 0, TD_LD * 4));
@@ -2686,16 +2671,9 @@ int bgamd_td_destroy(bgamd_td *td)
     if (!td) return BGAMD_OK;
     hipSetDevice(td->device);
     hipDeviceSynchronize();
-    TdView &v = td->v;
-    void *ptrs[] = {v.theta, v.w1t, v.e, v.fac, v.coef, v.sq, v.partial, v.gmeta, v.amask, v.anew, v.act_cols, v.wr_cols, v.nupd, v.qcur, v.wl3, v.lut, v.hid};
-    for (void *p : ptrs) if (p) hipFree(p);
     for (hipEvent_t e : td->ev) hipEventDestroy(e);
     bgamd_td_comm_destroy(td);
-    if (td->d_upd) hipFree(td->d_upd);
-    for (int k = 0; k < 2; ++k) { if (td->theta2[k]) hipFree(td->theta2[k]); if (td->wl3_2[k]) hipFree(td->wl3_2[k]); }
-    if (td->partial2) hipFree(td->partial2);
-    void *fit_ptrs[] = {td->fit_run, td->fit_part_sq, td->fit_part_cnt, td->fit_stat};
-    for (void *p : fit_ptrs) if (p) hipFree(p);
+    for (const TdBuf &b : td_buffers(td)) if (*b.ptr) hipFree(*b.ptr);
     delete td;
     return BGAMD_OK;
 }
@@ -2804,65 +2782,37 @@ int bgamd_td_step(bgamd_td *td, int64_t t, int64_t n_active, double alpha, float
         if (d_update) HIPCHK(hipMemsetAsync(d_update, 0, (size_t)TD_P * 4, s));
         return BGAMD_OK;
     }
-    // the scale of the stored traces (bg_learner.h): t = 0 writes ∇ at c = 1; afterwards c <- λ c, folded back in by an ordinary
-    // pass when it leaves [2^-40, 2^40] (λ > 1 is the caller's business, but it must not overflow either)
-    float emul = lambda, ginv = 1.0f, cmul = 1.0f;
-    int full = 1;
-    if (t == 0) td->scale = 1.0;
-    else {
-        const double c = (double)lambda * td->scale;
-        if (td->lazy && c >= 0x1p-40 && c <= 0x1p40) { td->scale = c; emul = 1.0f; ginv = (float)(1.0 / c); cmul = (float)c; full = 0; }
-        else { emul = (float)c; td->scale = 1.0; }
-    }
-    td->v.full_step = full;
+    const TdScale sc = td_scale_step(t, lambda, td->tune.lazy, td->scale);
+    td->v.full_step = sc.full;
     const TdView &v = td->v;
-    // mid-sized steps whose trace pass takes the pipelined whole-row kernel: forward pass and trace pass in ONE launch (bg_learner.h)
-    // slots per workgroup: the smallest of 1, 2, 4, 8, 16 that asks for no more workgroups than CUs (BGAMD_TD_FUSE_G pins it)
-    const long long fuse_groups_max = td->n_cu < TD_MAX_GROUPS ? td->n_cu : TD_MAX_GROUPS;
-    int fuse_g = td->fuse_g > 0 ? td->fuse_g : 1;
-    if (td->fuse_g <= 0) while (fuse_g < 16 && (n_active + fuse_g - 1) / fuse_g > fuse_groups_max) fuse_g *= 2;
-    // (BGAMD_TD_FUSED=0 / BGAMD_TD_DIRECT_MIN choose the forward kernel: a step that is to run the unfused or the VALU forward pass cannot take the
-    //  launch that contains the fused one)
-    const bool fused_step = td->fuse_step && td->pipe && td->fused && n_active >= td->direct_min && !td->no_wide_even && n_active >= td->fuse_min && n_active < td->mfma_min &&
-                            n_active < td->nt_min && (n_active + fuse_g - 1) / fuse_g <= fuse_groups_max;
-    if (fused_step) {
-    } else if (n_active >= td->mfma_min) {
-        // the [2 G x 198] · [198 x 128] product of the step on the matrix pipe (exact bf16 x 3 split of fc1.weight, fp32
-        // accumulation: the env's root pass), then the epilogue per game
-        const long long n_rows = 2 * n_active;
-        long long blocks = ((n_rows + 31) / 32 + ROOT3_THREADS / 64 - 1) / (ROOT3_THREADS / 64);
-        if (blocks > td->n_cu) blocks = td->n_cu;
-        hipLaunchKernelGGL(traj_hidden_bf16x3_kernel, dim3((unsigned)blocks), dim3(ROOT3_THREADS), ROOT3_LDS_TOTAL, s, v.rows,
-                           (const int4 *)v.gmeta, (long long)t, v.n_lanes, v.T, n_rows, (const uint4 *)v.wl3, (const uint2 *)v.lut,
-                           (const float *)(v.theta + TD_OFF_B1), v.hid);
-        hipLaunchKernelGGL(td_epilogue_wave_kernel, grid1(n_active, 4), dim3(256), 0, s, v, (long long)t, (long long)n_active, alpha);
-    } else if (n_active >= td->direct_min && td->fused) {
-        // mid-sized steps: the product and its epilogue in one launch (bg_learner.h)
-        hipLaunchKernelGGL(td_forward_mfma_kernel, grid1(n_active, TD_FUSED_GAMES), dim3(ROOT3D_THREADS), 0, s, v, (long long)t, (long long)n_active, alpha);
+    const TdPlan p = td_plan(td->tune, td->n_cu, t, n_active, sc.full);
+    const dim3 fgrid((unsigned)p.forward_grid);
+    switch (p.forward) {
+        case TdForward::NONE: break;
+        case TdForward::MATRIX_PIPE:
+            hipLaunchKernelGGL(traj_hidden_bf16x3_kernel, fgrid, dim3(ROOT3_THREADS), ROOT3_LDS_TOTAL, s, v.rows, (const int4 *)v.gmeta, (long long)t,
+                               v.n_lanes, v.T, 2 * n_active, (const uint4 *)v.wl3, (const uint2 *)v.lut, (const float *)(v.theta + TD_OFF_B1), v.hid);
+            hipLaunchKernelGGL(td_epilogue_wave_kernel, grid1(n_active, 4), dim3(256), 0, s, v, (long long)t, (long long)n_active, alpha);
+            break;
+        case TdForward::MFMA_FUSED:
+            hipLaunchKernelGGL(td_forward_mfma_kernel, fgrid, dim3(ROOT3D_THREADS), 0, s, v, (long long)t, (long long)n_active, alpha);
+            break;
+        case TdForward::DIRECT:
 #ifdef BGAMD_EXPERIMENTAL
-    } else if (n_active >= td->direct_min) {
-        // mid-sized steps: the same product, a workgroup per 32-row tile and the weight planes straight from the L2 (bg_eval.h)
-        const long long n_rows = 2 * n_active;
-        hipLaunchKernelGGL(traj_hidden_direct_kernel, dim3((unsigned)((n_rows + 31) / 32)), dim3(ROOT3D_THREADS), 0, s, v.rows,
-                           (const int4 *)v.gmeta, (long long)t, v.n_lanes, v.T, n_rows, (const uint4 *)v.wl3, (const uint2 *)v.lut,
-                           (const float *)(v.theta + TD_OFF_B1), v.hid);
-        hipLaunchKernelGGL(td_epilogue_wave_kernel, grid1(n_active, 4), dim3(256), 0, s, v, (long long)t, (long long)n_active, alpha);
+            hipLaunchKernelGGL(traj_hidden_direct_kernel, fgrid, dim3(ROOT3D_THREADS), 0, s, v.rows, (const int4 *)v.gmeta, (long long)t, v.n_lanes,
+                               v.T, 2 * n_active, (const uint4 *)v.wl3, (const uint2 *)v.lut, (const float *)(v.theta + TD_OFF_B1), v.hid);
+            hipLaunchKernelGGL(td_epilogue_wave_kernel, grid1(n_active, 4), dim3(256), 0, s, v, (long long)t, (long long)n_active, alpha);
+            break;
+#else
+            return BGAMD_E_INVALID;      // (not reached: only BGAMD_TD_FUSED=0 leads here, which this build does not read)
 #endif
-    } else if (n_active <= 8192)
-        hipLaunchKernelGGL((td_forward_kernel<2, false>), grid1(n_active, 2), dim3(128), 0, s, v, (long long)t, (long long)n_active, alpha);
-    else
-        hipLaunchKernelGGL((td_forward_kernel<4, false>), grid1(n_active, 4), dim3(128), 0, s, v, (long long)t, (long long)n_active, alpha);
-    // games per group: >= 4, and at most TD_MAX_GROUPS groups
-    long long ng = (n_active + TD_MAX_GROUPS - 1) / TD_MAX_GROUPS;
-#ifndef BG_TD_MIN_NG
-#define BG_TD_MIN_NG 4
-#endif
-    if (ng < BG_TD_MIN_NG) ng = BG_TD_MIN_NG;
-    if (td->slice_ng > 0 && n_active >= 512 && n_active < td->wide_min) {       // mid-sized steps on the slice kernel: fewer, larger groups
-        ng = td->slice_ng;                                                       //   (fewer partial rows for the reduce kernel to read)
-        if ((n_active + ng - 1) / ng > TD_MAX_GROUPS) ng = (n_active + TD_MAX_GROUPS - 1) / TD_MAX_GROUPS;
+        case TdForward::VALU2:
+            hipLaunchKernelGGL((td_forward_kernel<2, false>), fgrid, dim3(128), 0, s, v, (long long)t, (long long)n_active, alpha);
+            break;
+        case TdForward::VALU4:
+            hipLaunchKernelGGL((td_forward_kernel<4, false>), fgrid, dim3(128), 0, s, v, (long long)t, (long long)n_active, alpha);
+            break;
     }
-    int n_groups = (int)((n_active + ng - 1) / ng);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (td->timing) {
         if (td->ev_used * 2 + 2 > td->ev.size()) {
@@ -2873,60 +2823,47 @@ int bgamd_td_step(bgamd_td *td, int64_t t, int64_t n_active, double alpha, float
         td->ev_used++;
         HIPCHK(hipEventRecord(e0, s));
     }
-    // whole-row workgroups take chunks of TD_CHUNK games: below wide_min they pay only when the chunks divide evenly over the CUs
-    // (a streamed replay through 2 048 or 4 096 slots: 143 vs 147 and 110 vs 118 ms per 65 536-game round)
-    const long long per_wave_of_blocks = (long long)td->n_cu * TD_CHUNK;
-    const bool wide_even = !td->no_wide_even && n_active >= per_wave_of_blocks && td->wide_min > per_wave_of_blocks &&
-                           n_active * 20 >= ((n_active + per_wave_of_blocks - 1) / per_wave_of_blocks) * per_wave_of_blocks * 19;
-    if (n_active >= td->wide_min || wide_even || fused_step) {
-        // large rounds: a workgroup per whole trace row and strided chunks of games (bg_learner.h)
-        n_groups = (int)((n_active + TD_CHUNK - 1) / TD_CHUNK);
-        if (n_groups > td->n_cu) n_groups = td->n_cu;
-        if (n_groups > TD_MAX_GROUPS) n_groups = TD_MAX_GROUPS;
-        const bool nt = n_active >= td->nt_min;
-        if (fused_step) {
-            n_groups = (int)((n_active + fuse_g - 1) / fuse_g);
-#define BG_FUSED_LAUNCH(G)                                                                                                                   \
-    do {                                                                                                                                     \
-        if (t == 0)                                                                                                                          \
-            hipLaunchKernelGGL((td_step_fused_kernel<true, G>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)t,                  \
-                               (long long)n_active, alpha, emul, ginv, cmul, 1);                                                             \
-        else                                                                                                                                 \
-            hipLaunchKernelGGL((td_step_fused_kernel<false, G>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)t,                 \
-                               (long long)n_active, alpha, emul, ginv, cmul, full);                                                          \
+    // every trace kernel has a <true> (FIRST) instance for step 0 and takes the same tail of arguments
+    const dim3 tgrid(p.n_groups), wide(TD_WIDE_THREADS);
+#define BG_TRACE_LAUNCH(K_FIRST, K_LATER, grid, block, ...)                                                                \
+    do {                                                                                                                   \
+        if (p.first) hipLaunchKernelGGL(K_FIRST, grid, block, 0, s, v, __VA_ARGS__, sc.emul, sc.ginv, sc.cmul, p.full);    \
+        else hipLaunchKernelGGL(K_LATER, grid, block, 0, s, v, __VA_ARGS__, sc.emul, sc.ginv, sc.cmul, p.full);            \
     } while (0)
-            switch (fuse_g) {
+#define BG_FUSED_LAUNCH(G)                                                                                                 \
+    BG_TRACE_LAUNCH((td_step_fused_kernel<true, G>), (td_step_fused_kernel<false, G>), tgrid, wide, (long long)t, (long long)n_active, alpha)
+    switch (p.trace) {
+        case TdTrace::FUSED:
+            switch (p.fuse_g) {
                 case 1: BG_FUSED_LAUNCH(1); break;
                 case 2: BG_FUSED_LAUNCH(2); break;
                 case 4: BG_FUSED_LAUNCH(4); break;
                 case 8: BG_FUSED_LAUNCH(8); break;
                 default: BG_FUSED_LAUNCH(16); break;
             }
+            break;
+        case TdTrace::PIPE:
+            BG_TRACE_LAUNCH((td_trace_pipe_kernel<true>), (td_trace_pipe_kernel<false>), tgrid, wide, (long long)n_active);
+            break;
+        case TdTrace::WIDE_NT:
+            BG_TRACE_LAUNCH((td_trace_wide_kernel<true, true>), (td_trace_wide_kernel<false, true>), tgrid, wide, (long long)n_active);
+            break;
+        case TdTrace::WIDE:
+            hipLaunchKernelGGL((td_trace_wide_kernel<false, false>), tgrid, wide, 0, s, v, (long long)n_active, sc.emul, sc.ginv, sc.cmul, p.full);
+            break;
+        case TdTrace::SLICE:
+            BG_TRACE_LAUNCH(td_trace_kernel<true>, td_trace_kernel<false>, dim3(TD_SLICES, p.n_groups), dim3(TD_TRACE_THREADS), (long long)n_active,
+                            (int)p.ng);
+            break;
+    }
 #undef BG_FUSED_LAUNCH
-        } else if (td->pipe && !nt && n_active <= (long long)td->n_cu * TD_CHUNK * 4) {
-            // mid-sized steps (at most a few chunks per CU): the software-pipelined whole-row pass (bg_learner.h)
-            if (t == 0)
-                hipLaunchKernelGGL((td_trace_pipe_kernel<true>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)n_active, emul, ginv, cmul, 1);
-            else
-                hipLaunchKernelGGL((td_trace_pipe_kernel<false>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)n_active, emul, ginv, cmul, full);
-        } else if (t == 0)
-            hipLaunchKernelGGL((td_trace_wide_kernel<true, true>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)n_active, emul, ginv, cmul, 1);
-        else if (nt)
-            hipLaunchKernelGGL((td_trace_wide_kernel<false, true>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)n_active, emul, ginv, cmul, full);
-        else
-            hipLaunchKernelGGL((td_trace_wide_kernel<false, false>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)n_active, emul, ginv, cmul, full);
-    } else if (t == 0)
-        hipLaunchKernelGGL(td_trace_kernel<true>, dim3(TD_SLICES, n_groups), dim3(TD_TRACE_THREADS), 0, s, v, (long long)n_active,
-                           (int)ng, emul, ginv, cmul, 1);
-    else
-        hipLaunchKernelGGL(td_trace_kernel<false>, dim3(TD_SLICES, n_groups), dim3(TD_TRACE_THREADS), 0, s, v, (long long)n_active,
-                           (int)ng, emul, ginv, cmul, full);
+#undef BG_TRACE_LAUNCH
     if (td->timing) {
         HIPCHK(hipEventRecord(e1, s));
         td->trace_launches++;
         td->trace_game_steps += (uint64_t)n_active;
     }
-    hipLaunchKernelGGL(td_reduce_kernel, grid1(TD_P, 64), dim3(256), 0, s, v, n_groups, d_update, d_update ? 0 : 1);
+    hipLaunchKernelGGL(td_reduce_kernel, grid1(TD_P, 64), dim3(256), 0, s, v, p.n_groups, d_update, d_update ? 0 : 1);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
@@ -2941,7 +2878,7 @@ int bgamd_td_apply(bgamd_td *td, const float *d_update, void *stream)
     return BGAMD_OK;
 }
 
-// The supervised step (bg_fit.h): rows and targets -> update = Σ_i fp32(alpha · (y_i - V(x_i))) ∇V(x_i), in chunks of td->fit_chunk rows;
+// The supervised step (bg_fit.h): rows and targets -> update = Σ_i fp32(alpha · (y_i - V(x_i))) ∇V(x_i), in chunks of td->tune.fit_chunk rows;
 // every chunk is fit_step_kernel + fit_reduce_kernel, the last reduce hands the update out or applies it.  Stream-ordered, no host wait;
 // touches nothing of a replay's state but the partial sums, which are free between replays.
 int bgamd_td_fit_step(bgamd_td *td, const void *d_rows, const float *d_target, int64_t n, double alpha, float *d_update, void *stream)
@@ -2955,7 +2892,7 @@ int bgamd_td_fit_step(bgamd_td *td, const void *d_rows, const float *d_target, i
         if (d_update) HIPCHK(hipMemsetAsync(d_update, 0, (size_t)TD_P * 4, s));
         return BGAMD_OK;
     }
-    const long long chunk = td->fit_chunk;
+    const long long chunk = td->tune.fit_chunk;
     const long long n_chunks = (n + chunk - 1) / chunk;
     for (long long c = 0; c < n_chunks; ++c) {
         const long long r0 = c * chunk;
@@ -2968,7 +2905,7 @@ int bgamd_td_fit_step(bgamd_td *td, const void *d_rows, const float *d_target, i
         f.theta = td->v.theta; f.w1t = td->v.w1t;
         f.partial = td->v.partial;
         f.part_sq = td->fit_part_sq; f.part_cnt = td->fit_part_cnt;
-        const int groups = f.tiles < td->fit_groups ? f.tiles : td->fit_groups;
+        const int groups = f.tiles < td->tune.fit_groups ? f.tiles : (int)td->tune.fit_groups;
         hipLaunchKernelGGL(fit_step_kernel, dim3(groups), dim3(FIT_THREADS), 0, s, f, alpha);
         const int last = c + 1 == n_chunks ? 1 : 0;
         hipLaunchKernelGGL(fit_reduce_kernel, grid1(TD_P, 64), dim3(256), 0, s, td->v, groups, td->fit_run, c == 0 ? 1 : 0, last, d_update,
@@ -2998,30 +2935,17 @@ int bgamd_td_fit_stats(bgamd_td *td, double *h_sq_sum, int64_t *h_rows, int64_t 
 }  // extern "C"
 
 namespace {
-// slots per workgroup of the fused launch for a step of n_active slots (0: the step does not take the fused launch)
-int td_fuse_g_for(const bgamd_td *td, long long n_active)
-{
-    const long long fuse_groups_max = td->n_cu < TD_MAX_GROUPS ? td->n_cu : TD_MAX_GROUPS;
-    int fuse_g = td->fuse_g > 0 ? td->fuse_g : 1;
-    if (td->fuse_g <= 0) while (fuse_g < 16 && (n_active + fuse_g - 1) / fuse_g > fuse_groups_max) fuse_g *= 2;
-    const bool ok = td->fuse_step && td->pipe && td->fused && n_active >= td->direct_min && !td->no_wide_even && n_active >= td->fuse_min &&
-                    n_active < td->mfma_min && n_active < td->nt_min && (n_active + fuse_g - 1) / fuse_g <= fuse_groups_max;
-    return ok ? fuse_g : 0;
-}
-
 // The delayed replay: every step ONE launch of td_step_fused_kernel<., ., DELAY = true> (bg_learner.h).  Step t reads weight buffer t & 1 and the
 // partial sums of step t - 1, writes weight buffer (t + 1) & 1 and its own partial sums (set t & 1); one flush launch at the end applies the last
 // update and leaves the result in the learner's canonical buffers.
 int td_replay_delayed(bgamd_td *td, int64_t n_steps, long long k, int fuse_g, double alpha, float lambda, hipStream_t s)
 {
-    if (!td->theta2[0]) {
+    if (!td->partial2) {                 // (the last of its buffers in the list: there once all of them are)
+        if (const int rc = td_alloc(td, TD_AT_DELAY)) return rc;
         for (int b = 0; b < 2; ++b) {
-            HIPCHK(hipMalloc((void **)&td->theta2[b], (size_t)TD_LD * 4));
             HIPCHK(hipMemset(td->theta2[b], 0, (size_t)TD_LD * 4));
-            HIPCHK(hipMalloc((void **)&td->wl3_2[b], 3 * EVAL16_W_BYTES));
             HIPCHK(hipMemset(td->wl3_2[b], 0, 3 * EVAL16_W_BYTES));
         }
-        HIPCHK(hipMalloc((void **)&td->partial2, ((size_t)TD_MAX_GROUPS * TD_LD + 64) * 4));
         HIPCHK(hipMemset(td->partial2, 0, ((size_t)TD_MAX_GROUPS * TD_LD + 64) * 4));
     }
     td->last_stream = s;
@@ -3030,16 +2954,9 @@ int td_replay_delayed(bgamd_td *td, int64_t n_steps, long long k, int fuse_g, do
     float *part[2] = {td->v.partial, td->partial2};
     const int n_groups = (int)((k + fuse_g - 1) / fuse_g);
     for (int64_t t = 0; t < n_steps; ++t) {
-        float emul = lambda, ginv = 1.0f, cmul = 1.0f;                 // (the scale of the stored traces: as bgamd_td_step)
-        int full = 1;
-        if (t == 0) td->scale = 1.0;
-        else {
-            const double c = (double)lambda * td->scale;
-            if (td->lazy && c >= 0x1p-40 && c <= 0x1p40) { td->scale = c; emul = 1.0f; ginv = (float)(1.0 / c); cmul = (float)c; full = 0; }
-            else { emul = (float)c; td->scale = 1.0; }
-        }
+        const TdScale sc = td_scale_step(t, lambda, td->tune.lazy, td->scale);
         TdView v = td->v;
-        v.full_step = full;
+        v.full_step = sc.full;
         v.theta = td->theta2[t & 1];
         v.wl3 = td->wl3_2[t & 1];
         v.partial = part[t & 1];
@@ -3051,10 +2968,10 @@ int td_replay_delayed(bgamd_td *td, int64_t n_steps, long long k, int fuse_g, do
     do {                                                                                                                                     \
         if (t == 0)                                                                                                                          \
             hipLaunchKernelGGL((td_step_fused_kernel<true, G, true>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)t,           \
-                               (long long)k, alpha, emul, ginv, cmul, 1, pprev, n_prev, thn, wln);                                           \
+                               (long long)k, alpha, sc.emul, sc.ginv, sc.cmul, 1, pprev, n_prev, thn, wln);                                  \
         else                                                                                                                                 \
             hipLaunchKernelGGL((td_step_fused_kernel<false, G, true>), dim3(n_groups), dim3(TD_WIDE_THREADS), 0, s, v, (long long)t,          \
-                               (long long)k, alpha, emul, ginv, cmul, full, pprev, n_prev, thn, wln);                                        \
+                               (long long)k, alpha, sc.emul, sc.ginv, sc.cmul, sc.full, pprev, n_prev, thn, wln);                            \
     } while (0)
         switch (fuse_g) {
             case 1: BG_DELAY_LAUNCH(1); break;
@@ -3087,13 +3004,13 @@ int bgamd_td_replay(bgamd_td *td, int64_t n_steps, const int64_t *h_n_active, do
     if (!td || !h_n_active || n_steps < 0 || (td->begun && !td->stream_mode && n_steps > td->v.T)) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(td->device));
     if (td->delay && td->begun && td->stream_mode && td->has_weights && n_steps > 0) {
-        // the one-launch step exists for the steps that take the fused launch with at least TD_DELAY_SLICES workgroups: a streamed replay through a
-        // constant number of slots in that range (512 ... 4 096 on 256 CUs).  Anything else replays exactly, update by update.
+        // a streamed replay through a constant number of slots may take the one-launch step (td_delay_g).  Anything else replays exactly, update
+        // by update.
         bool same = true;
         for (int64_t t = 1; t < n_steps; ++t) same = same && h_n_active[t] == h_n_active[0];
         const long long k = h_n_active[0];
-        const int g = same && k > 0 && k <= td->v.n_games ? td_fuse_g_for(td, k) : 0;
-        if (g > 0 && (k + g - 1) / g >= TD_DELAY_SLICES) return td_replay_delayed(td, n_steps, k, g, alpha, lambda, (hipStream_t)stream);
+        const int g = same && k <= td->v.n_games ? td_delay_g(td->tune, td->n_cu, k) : 0;
+        if (g > 0) return td_replay_delayed(td, n_steps, k, g, alpha, lambda, (hipStream_t)stream);
     }
     for (int64_t t = 0; t < n_steps; ++t) {
         if (h_n_active[t] == 0) continue;
@@ -3106,7 +3023,6 @@ int bgamd_td_replay(bgamd_td *td, int64_t n_steps, const int64_t *h_n_active, do
 int bgamd_td_stats(bgamd_td *td, double *h_sq_sum, int64_t *h_updates)
 {
     ENV_GUARD(td);
-    HIPCHK(hipSetDevice(td->device));
     HIPCHK(hipStreamSynchronize(td->last_stream));
     if (h_sq_sum) {
         std::vector<double> sq((size_t)td->v.n_games);
@@ -3116,11 +3032,9 @@ int bgamd_td_stats(bgamd_td *td, double *h_sq_sum, int64_t *h_updates)
         *h_sq_sum = acc;
     }
     if (h_updates) {
-        std::vector<unsigned int> c((size_t)td->v.n_games);
-        if (!c.empty()) HIPCHK(td_read(td, c.data(), td->v.nupd, c.size() * 4));
-        int64_t tot = 0;
-        for (unsigned int x : c) tot += x;
-        *h_updates = tot;
+        uint64_t updates = 0;
+        if (const int rc = td_sum_slots(td, td->v.nupd, &updates)) return rc;
+        *h_updates = (int64_t)updates;
     }
     return BGAMD_OK;
 }
@@ -3130,12 +3044,7 @@ int bgamd_td_active_columns(bgamd_td *td, uint64_t *h_columns)
     if (!td || !h_columns) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(td->device));
     HIPCHK(hipStreamSynchronize(td->last_stream));
-    std::vector<unsigned int> c((size_t)td->v.n_games);
-    if (!c.empty()) HIPCHK(td_read(td, c.data(), td->v.act_cols, c.size() * 4));
-    uint64_t tot = 0;
-    for (unsigned int x : c) tot += x;
-    *h_columns = tot;
-    return BGAMD_OK;
+    return td_sum_slots(td, td->v.act_cols, h_columns);
 }
 
 int bgamd_td_slots(bgamd_td *td, int32_t *h_out)
@@ -3165,12 +3074,7 @@ int bgamd_td_written_columns(bgamd_td *td, uint64_t *h_columns)
     if (!td || !h_columns) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(td->device));
     HIPCHK(hipStreamSynchronize(td->last_stream));
-    std::vector<unsigned int> c((size_t)td->v.n_games);
-    if (!c.empty()) HIPCHK(td_read(td, c.data(), td->v.wr_cols, c.size() * 4));
-    uint64_t tot = 0;
-    for (unsigned int x : c) tot += x;
-    *h_columns = tot;
-    return BGAMD_OK;
+    return td_sum_slots(td, td->v.wr_cols, h_columns);
 }
 
 int bgamd_td_time(bgamd_td *td, int enable)
@@ -3245,6 +3149,16 @@ RcclApi *rccl_api()
             return BGAMD_E_HIP;                                                             \
         }                                                                                   \
     } while (0)
+
+// the tail of a multi-rank step: the rank's update in d_upd -> all-reduced in place -> applied, on the step's stream
+int td_allreduce_apply(bgamd_td *td, hipStream_t s)
+{
+    RcclApi *api = rccl_api();
+    RCCLCHK(api, api->AllReduce(td->d_upd, td->d_upd, (size_t)TD_P, ncclFloat32, ncclSum, (ncclComm_t)td->comm, s));
+    hipLaunchKernelGGL(td_apply_kernel, grid1(TD_P, 256), dim3(256), 0, s, td->v, (const float *)td->d_upd, 0);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3268,7 +3182,7 @@ int bgamd_td_comm_init(bgamd_td *td, const uint8_t h_id[128], int rank, int worl
     RcclApi *api = rccl_api();
     if (!api) return BGAMD_E_HIP;
     bgamd_td_comm_destroy(td);
-    if (!td->d_upd) HIPCHK(hipMalloc((void **)&td->d_upd, (size_t)TD_P * 4));
+    if (const int rc = td_alloc(td, TD_AT_COMM)) return rc;
     ncclUniqueId id;
     memcpy(&id, h_id, 128);
     ncclComm_t comm = nullptr;
@@ -3303,11 +3217,7 @@ int bgamd_td_step_allreduce(bgamd_td *td, int64_t t, int64_t n_active, double al
         HIPCHK(hipMemsetAsync(td->d_upd, 0, (size_t)TD_P * 4, s));
         td->last_stream = s;
     }
-    RcclApi *api = rccl_api();
-    RCCLCHK(api, api->AllReduce(td->d_upd, td->d_upd, (size_t)TD_P, ncclFloat32, ncclSum, (ncclComm_t)td->comm, s));
-    hipLaunchKernelGGL(td_apply_kernel, grid1(TD_P, 256), dim3(256), 0, s, td->v, (const float *)td->d_upd, 0);
-    HIPCHK(hipGetLastError());
-    return BGAMD_OK;
+    return td_allreduce_apply(td, s);
 }
 
 // the supervised step of a multi-rank fit: fit step with the update handed out -> ncclAllReduce -> apply, as bgamd_td_step_allreduce
@@ -3316,12 +3226,7 @@ int bgamd_td_fit_step_allreduce(bgamd_td *td, const void *d_rows, const float *d
     if (!td || !td->comm || !td->d_upd) return BGAMD_E_INVALID;
     const int rc = bgamd_td_fit_step(td, d_rows, d_target, n, alpha, td->d_upd, stream);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    RcclApi *api = rccl_api();
-    RCCLCHK(api, api->AllReduce(td->d_upd, td->d_upd, (size_t)TD_P, ncclFloat32, ncclSum, (ncclComm_t)td->comm, s));
-    hipLaunchKernelGGL(td_apply_kernel, grid1(TD_P, 256), dim3(256), 0, s, td->v, (const float *)td->d_upd, 0);
-    HIPCHK(hipGetLastError());
-    return BGAMD_OK;
+    return td_allreduce_apply(td, (hipStream_t)stream);
 }
 
 int bgamd_td_replay_allreduce(bgamd_td *td, int64_t n_steps, const int64_t *h_n_active, int64_t n_own_steps, double alpha, float lambda,

@@ -394,7 +394,7 @@ def _streamed(theta0, logname, lam, slots, ring, dtype, mutate, bound, alpha, ag
 
 
 def scale_passes(lam, n):
-    """The scale c of the lazily stored traces over n steps, as bgamd_td_step keeps it (csrc/bgamd.hip: `if (t == 0) td->scale = 1.0`,
+    """The scale c of the lazily stored traces over n steps, as bgamd_td_step keeps it (td_scale_step of csrc/bg_td_plan.h: `if (t == 0) scale = 1.0`,
     then c = λ·scale is kept while `c >= 0x1p-40 && c <= 0x1p40`, else an ordinary pass folds it back and the scale returns to 1)
     -> (the steps that are ordinary passes, the scales reached in between)"""
     c, full, reached = 1.0, [], []

@@ -13,38 +13,12 @@ import pytest
 
 import learner_ref as LR
 import nets as N
+from learner_routes import ROUTES, _VARS
 from test_gpu_parity import _np
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-# Kernel routes: the BGAMD_TD_* variables bgamd_td_create reads, and the kernels bgamd_td_step's dispatch then selects for steps of
-# 157 ... 1 running games (lock-step) or 7 slots (streamed) -- far below every default threshold (direct_min = fuse_min = 512,
-# wide_min = nt_min = 8192, mfma_min = 24576).  Step 0 runs the <true> (FIRST) instance of the trace kernel named.
-ROUTES = {
-    # n < direct_min: td_forward_kernel<2>; n < wide_min: td_trace_kernel
-    "valu": {},
-    # n >= direct_min: td_forward_mfma_kernel; FUSE_STEP=0 keeps the step out of the fused launch; n < wide_min: td_trace_kernel
-    "direct_slice": {"BGAMD_TD_DIRECT_MIN": "1", "BGAMD_TD_FUSE_STEP": "0"},
-    # n >= mfma_min: traj_hidden_bf16x3_kernel + td_epilogue_wave_kernel (and never the fused launch); td_trace_kernel
-    "matrix_pipe": {"BGAMD_TD_MFMA_MIN": "1"},
-    # td_forward_mfma_kernel; n >= wide_min, pipe, n < nt_min: td_trace_pipe_kernel
-    "direct_pipe": {"BGAMD_TD_DIRECT_MIN": "1", "BGAMD_TD_FUSE_STEP": "0", "BGAMD_TD_WIDE_MIN": "1"},
-    # ... PIPE=0: td_trace_wide_kernel<., false> (step 0: <true, true>)
-    "direct_wide": {"BGAMD_TD_DIRECT_MIN": "1", "BGAMD_TD_FUSE_STEP": "0", "BGAMD_TD_WIDE_MIN": "1", "BGAMD_TD_PIPE": "0"},
-    # ... n >= nt_min: td_trace_wide_kernel<false, true>, the nontemporal instance
-    "direct_wide_nt": {"BGAMD_TD_DIRECT_MIN": "1", "BGAMD_TD_FUSE_STEP": "0", "BGAMD_TD_WIDE_MIN": "1", "BGAMD_TD_PIPE": "0",
-                       "BGAMD_TD_NT_MIN": "1"},
-    # n >= direct_min, n >= fuse_min, ceil(n / G) <= CUs: td_step_fused_kernel<., 1>, one slot per workgroup
-    "fused_g1": {"BGAMD_TD_DIRECT_MIN": "1", "BGAMD_TD_FUSE_MIN": "1", "BGAMD_TD_FUSE_G": "1"},
-    # ... td_step_fused_kernel<., 16>: 16 slots per workgroup, the last workgroup partly filled
-    "fused_g16": {"BGAMD_TD_DIRECT_MIN": "1", "BGAMD_TD_FUSE_MIN": "1", "BGAMD_TD_FUSE_G": "16"},
-    # the valu route with e <- λ e + ∇ at every step (emul = λ, every pass an ordinary one)
-    "ordinary": {"BGAMD_TD_LAZY": "0"},
-}
-_VARS = ("BGAMD_TD_DIRECT_MIN", "BGAMD_TD_FUSE_STEP", "BGAMD_TD_MFMA_MIN", "BGAMD_TD_WIDE_MIN", "BGAMD_TD_PIPE", "BGAMD_TD_NT_MIN",
-         "BGAMD_TD_FUSE_MIN", "BGAMD_TD_FUSE_G", "BGAMD_TD_LAZY", "BGAMD_TD_DENSE", "BGAMD_TD_NG", "BGAMD_TD_NO_WIDE_EVEN", "BGAMD_TD_FUSED")
 
 _FAMILY_ROUTE = [(f, r) for f in N.PARITY for r in ROUTES]     # family-major: the routes of a family share its cached reference
 

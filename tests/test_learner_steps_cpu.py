@@ -125,11 +125,15 @@ def test_every_column_switches_on_late_off_and_on_again():
 
 
 def test_lazy_scale_folds_back_twice_at_a_quarter():
-    """learner_ref.scale_passes restates bgamd_td_step's scale bookkeeping; the source line it mirrors is checked to be there (the device
+    """learner_ref.scale_passes restates bgamd_td_step's scale bookkeeping (td_scale_step of csrc/bg_td_plan.h); the source line it mirrors is checked to be there (the device
     side of the claim: test_lambda_edges of tests/test_gpu_learner_steps.py)."""
-    src = open(os.path.join(os.path.dirname(__file__), "..", "backgammon-engine_amd", "csrc", "bgamd.hip")).read()
+    csrc = os.path.join(os.path.dirname(__file__), "..", "backgammon-engine_amd", "csrc")
+    src = open(os.path.join(csrc, "bgamd.hip")).read()
     step = src[src.index("int bgamd_td_step("):src.index("int bgamd_td_apply(")]
-    assert "if (t == 0) td->scale = 1.0;" in step and "c >= 0x1p-40 && c <= 0x1p40" in step and "td->scale = 1.0; }" in step
+    assert "td_scale_step(t, lambda, td->tune.lazy, td->scale)" in step           # the bookkeeping itself: bg_td_plan.h, for both replays
+    plan = open(os.path.join(csrc, "bg_td_plan.h")).read()
+    scale = plan[plan.index("inline TdScale td_scale_step("):plan.index("// ---- the fused launch ----")]
+    assert "if (t == 0) scale = 1.0;" in scale and "c >= 0x1p-40 && c <= 0x1p40" in scale and "scale = 1.0; }" in scale
     full, reached = LR.scale_passes(0.25, 48)
     assert full == [0, 21, 42] and min(reached) == 2.0 ** -40    # the inclusive end of the range is reached, the next step folds
     assert LR.scale_passes(0.0, 48)[0] == list(range(48)) and LR.scale_passes(1.0, 48)[0] == [0]

@@ -48,3 +48,22 @@ def test_library_host_code_under_asan_ubsan(tmp_path):
     r = subprocess.run([str(exe)], env=dict(os.environ, **SAN_ENV), capture_output=True, text=True, timeout=300)
     _clean(r)
     assert r.stdout.startswith("OK")
+
+
+def test_learner_step_plan_under_asan_ubsan(tmp_path):
+    """The learner's step plan, trace scale and environment parser (csrc/bg_td_plan.h, plain C++) compiled with the sanitizers into
+    tests/sanitize/td_plan_driver.cpp and run over the sweep of tests/test_td_plan_cpu.py: every tuning, both builds' parsers, three CU
+    counts, every step size at which a route can change; what the plans SAY is that module's business."""
+    import test_td_plan_cpu as P
+    exe = P.build_driver(tmp_path / "td_plan_driver", ("-fsanitize=address,undefined", "-fno-omit-frame-pointer"))
+    for env in P.tunings():
+        for experimental in (False, True):
+            assert len(P.run(exe, ["tuning", int(experimental)], env, extra_env=SAN_ENV)) == 15
+            for n_cu in P.N_CUS:
+                sizes = P.step_sizes(n_cu)
+                pairs = "".join("%d %d\n" % (t, n) for t in P.STEPS for n in sizes)
+                assert len(P.run(exe, ["plan", int(experimental), n_cu], env, pairs, SAN_ENV)) == 3 * len(sizes)
+                assert len(P.run(exe, ["delay", int(experimental), n_cu], env, "".join("%d\n" % n for n in sizes), SAN_ENV)) == len(sizes)
+    for lam in ("0", "0.25", "0.699999988", "1", "1.5"):
+        for lazy in ({}, {"BGAMD_TD_LAZY": "0"}):
+            assert len(P.run(exe, ["scale", lam, 400], lazy, extra_env=SAN_ENV)) == 400
