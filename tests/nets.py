@@ -105,6 +105,27 @@ def table(name, seed=SEED):
     return _cache[key]
 
 
+def dyadic_table(seed, n_cols=16):
+    """A table under which candidates tie EXACTLY, in float32 and in fp64, in any order of summation (tests/search_model.py, the search's
+    tie rules): W1 is zero except on n_cols columns drawn from features 0..191 -- the point features, whose values are 0, 1/2, 1, ... --
+    with entries k / 16, k an integer in [-8, 8]; b1 of the same kind; W2 = 0.3 x normal; b2 = 0.  Every hidden pre-activation is then a
+    sum of multiples of 1/32 below 2^7: exact whatever the order, so two candidates that agree on the chosen columns get the same value
+    bit for bit.  Not a member of PARITY / EDGE / NAMES.  (float32 [25601], read-only and cached like table().)"""
+    key = ("dyadic", seed, n_cols)
+    if key not in _cache:
+        rng = np.random.RandomState(seed)
+        cols = np.sort(rng.choice(192, n_cols, replace=False))
+        W1 = np.zeros((N_HID, N_IN), np.float32)
+        W1[:, cols] = rng.randint(-8, 9, (N_HID, n_cols)).astype(np.float32) / np.float32(16)
+        w = np.zeros(N_PARAMS, np.float32)
+        w[:O1] = W1.ravel()
+        w[O1:O2] = rng.randint(-8, 9, N_HID).astype(np.float32) / np.float32(16)
+        w[O2:O3] = (0.3 * rng.standard_normal(N_HID)).astype(np.float32)
+        w.setflags(write=False)
+        _cache[key] = w
+    return _cache[key]
+
+
 def reference_table(name):
     """The table the fp64 references play with.  out_lo's fp64 values are ~1e-90 apart instead of equal -- differences no float32
     evaluator can see, yet enough for an fp64 arg-min to prefer another candidate -- so its references run with b2 = -800, where
