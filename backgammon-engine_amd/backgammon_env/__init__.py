@@ -304,6 +304,30 @@ class VecGame:
             _capi.check(self._lib.bgamd_env_search_read(self._h, _ptr(st), _ptr(v1), _ptr(v2), None, _stream()), "search_read")
         return st, v1, v2, kept
 
+    ANALYSIS_FIELDS = (("status", torch.int32), ("distinct", torch.int32), ("rank1", torch.int32), ("rank2", torch.int32),
+                       ("v1_played", torch.float32), ("v1_best", torch.float32), ("v2_played", torch.float32),
+                       ("v2_best", torch.float32), ("error", torch.float32))
+
+    def analyze_moves(self, played, top_k=4, only_player=None, slot=0):
+        """Move analysis (include/bgamd.h, bgamd_env_analyze_moves): `played` [n, 28] is the afterstate played from each lane's current
+        board, side to move and dice; it is judged against a 2-ply search over the top_k best afterstates by the net (0 = all) and
+        itself.  Nothing is applied.  -> dict of device tensors [n]: status (0 analysed, 1 idle, 2 no move, 3 not an afterstate), distinct,
+        rank1, rank2, v1_played, v1_best, v2_played, v2_best, error, best [n, 28], summary_raw (float64 [12]) -- and summary, the same
+        twelve numbers by name: player1 / player2 -> decisions, unforced, mistakes, error_sum, max_error; no_move; not_found
+        (synchronises for them)."""
+        st = self._dev(played, torch.int32, (self.n, 28))
+        _capi.check(self._lib.bgamd_env_analyze_moves(self._h, self._flags(False, False, False, only_player, slot), int(top_k), _ptr(st),
+                                                      _stream()), "analyze_moves")
+        out = {k: self._buf((self.n,), dt) for k, dt in self.ANALYSIS_FIELDS}
+        out["best"] = self._buf((self.n, 28), torch.int32)
+        out["summary_raw"] = self._buf((12,), torch.float64)
+        _capi.check(self._lib.bgamd_env_analysis_read(self._h, *[_ptr(out[k]) for k, _ in self.ANALYSIS_FIELDS], _ptr(out["best"]),
+                                                      _ptr(out["summary_raw"]), _stream()), "analysis_read")
+        s = out["summary_raw"].cpu().tolist()             # (synchronises: `st` may be a temporary)
+        side = lambda v: {"decisions": int(v[0]), "unforced": int(v[1]), "mistakes": int(v[2]), "error_sum": v[3], "max_error": v[4]}
+        out["summary"] = {"player1": side(s[0:5]), "player2": side(s[5:10]), "no_move": int(s[10]), "not_found": int(s[11])}
+        return out
+
     def evaluate_preroll(self, states28, turn, slot=0):
         """1-ply pre-roll evaluation (include/bgamd.h, bgamd_env_evaluate_preroll): for each position with `turn` to roll, the value of the
         greedy step's choice for each of the 21 rolls in ROLLS' order (the net's value of the position when the roll has no move; the

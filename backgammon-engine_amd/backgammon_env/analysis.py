@@ -1,5 +1,8 @@
-"""Move analysis on top of the env: which of a turn's moves is best by rollout (include/bgamd.h, bgamd_env_rollout)."""
+"""Move analysis on top of the env: which of a turn's moves is best by rollout (include/bgamd.h, bgamd_env_rollout), and how much a
+player's moves lose against a 2-ply judge (bgamd_env_analyze_moves)."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -54,3 +57,47 @@ def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, s
     key = "vr_mean" if variance_reduction else "mean"
     out.sort(key=lambda c: -c[key] if mover == 0 else c[key])
     return out
+
+
+def error_rate(player, judge, turns, top_k=4, epsilon=0.0, player_slot=0, judge_slot=0, on_turn=None):
+    """How much the player's moves lose by the judge's 2-ply search, over `turns` turns of every lane of `player`.
+
+    player, judge: two VecGames with the same lane count; the player's weights in its slot player_slot play (one greedy step per turn
+    with rolled dice, exploring with probability epsilon), the judge's weights in its slot judge_slot judge.  Each turn the judge's lanes
+    are set to the player's boards, sides to move and the dice the step played, and analyze_moves(top_k) scores the boards the step
+    reached (a game that ends stays on its final board for this, then restarts).  The judge is never stepped; the player plays on from
+    wherever it stands and is left wherever the last turn took it.
+    on_turn(turn, player, result): called after every turn's analysis with the analyze_moves result (device tensors).
+
+    -> dict: player1 / player2 / total, each a dict of
+         decisions (moves analysed), unforced (of those: more than one afterstate), mistakes (error > 0), error_sum,
+         error_rate = error_sum / unforced, agreement = 1 - mistakes / unforced (nan without an unforced decision),
+         passes (turns without a legal move), illegal (played boards the judge does not list: must be 0), idle (lanes that took no part)
+       and lane_turns = lanes x turns = decisions + passes + illegal + idle of total."""
+    if player.n != judge.n:
+        raise ValueError("error_rate needs two VecGames of equal lane count")
+    import torch
+    counts = np.zeros((2, 6), np.int64)                    # per mover: decisions, unforced, mistakes, passes, illegal, idle
+    sums = ([], [])
+    for t in range(int(turns)):
+        pre, mover = player.states(), player.turns()
+        player.step_greedy(roll=True, auto_reset=False, epsilon=epsilon, slot=player_slot)
+        judge.set_states(pre, mover)
+        judge.set_dice(player.dice())
+        res = judge.analyze_moves(player.states(), top_k=top_k, slot=judge_slot)
+        by = torch.bincount(res["status"].long() * 2 + mover.long(), minlength=8).cpu().numpy().reshape(4, 2)
+        for side, name in enumerate(("player1", "player2")):
+            s = res["summary"][name]
+            counts[side] += (s["decisions"], s["unforced"], s["mistakes"], by[2, side], by[3, side], by[1, side])
+            sums[side].append(s["error_sum"])
+        if on_turn is not None:
+            on_turn(t, player, res)
+        player.reset(mask=(player.flags() & 4) != 0)
+
+    def side(c, err):
+        unforced = int(c[1])
+        return {"decisions": int(c[0]), "unforced": unforced, "mistakes": int(c[2]), "error_sum": err,
+                "error_rate": err / unforced if unforced else math.nan, "agreement": 1.0 - int(c[2]) / unforced if unforced else math.nan,
+                "passes": int(c[3]), "illegal": int(c[4]), "idle": int(c[5])}
+    return {"player1": side(counts[0], math.fsum(sums[0])), "player2": side(counts[1], math.fsum(sums[1])),
+            "total": side(counts.sum(0), math.fsum(sums[0] + sums[1])), "lane_turns": player.n * int(turns)}

@@ -642,6 +642,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 #include "bg_rollout.h"
 #include "bg_vr.h"
 #include "bg_health.h"
+#include "bg_analysis.h"
 
 }  // namespace
 
@@ -744,6 +745,28 @@ struct SearchState {
     void release() { free_all({cnt, off, fill, kept, koff, max, grp, rank, c_rows, c_key, c_v1, c_v2, c_rval}); *this = SearchState{}; }
 };
 
+// move analysis (bgamd_env_analyze_moves, bg_analysis.h): the per-lane results of the last one and its summary
+struct AnalysisState {
+    AnaView v{};
+    double *summary = nullptr;             // [ANA_SUMMARY]
+    bool ready = false;                    // an analysis has run and nothing has failed since (bgamd_env_analysis_read)
+    int allocate(long long n)
+    {
+        release();                                         // (what an allocation that failed half-way left)
+        if (int rc = alloc_buffers(n, {{(void **)&v.status, 4}, {(void **)&v.distinct, 4}, {(void **)&v.rank1, 4}, {(void **)&v.rank2, 4},
+                                       {(void **)&v.v1_played, 4}, {(void **)&v.v1_best, 4}, {(void **)&v.v2_played, 4}, {(void **)&v.v2_best, 4},
+                                       {(void **)&v.error, 4}, {(void **)&v.best, 32}, {(void **)&v.ppos, 4}, {(void **)&v.pslot, 4}}))
+            return rc;
+        HIPCHK(hipMalloc(&summary, ANA_SUMMARY * 8));       // last: summary != NULL says that every buffer is there
+        return BGAMD_OK;
+    }
+    void release()
+    {
+        free_all({v.status, v.distinct, v.rank1, v.rank2, v.v1_played, v.v1_best, v.v2_played, v.v2_best, v.error, v.best, v.ppos, v.pslot, summary});
+        *this = AnalysisState{};
+    }
+};
+
 // Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h), and what the luck-adjusted ones add (bg_vr.h)
 struct RolloutState {
     uint4 *pos = nullptr, *fan = nullptr, *trows = nullptr;        // [cap_pos], [cap_fan], [cap_lanes]
@@ -838,6 +861,7 @@ struct bgamd_env {
     // whole number of 16-byte units, so that the rollout's one fill launch clears both.  48 bytes, allocated with every env (env_allocate).
     unsigned long long *a_ctr = nullptr;
     SearchState srch;
+    AnalysisState ana;
     RolloutState ro;
     PrerollState pre;
     uint32_t *spread = nullptr;            // [5][n] per-lane words of bgamd_env_choice_spread (bg_health.h, SpreadView)
@@ -1087,6 +1111,7 @@ int bgamd_env_destroy(bgamd_env *env)
     HIPCHK(hipSetDevice(env->device));
     if (!env->borrows_weights) net_tables(env->net, false);        // (a scratch env's are its parent's)
     env->srch.release();
+    env->ana.release();
     env->ro.release();
     env->pre.release();
     const EnvView &v = env->v;
@@ -1834,17 +1859,21 @@ static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int
     return (h & ERRF_STATE) ? BGAMD_E_STATE : BGAMD_OK;
 }
 
-// ---- 2-ply expectimax (bg_search.h) ---------------------------------------------------------------------------------------
-int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
+// ---- 2-ply expectimax (bg_search.h) and the move analysis built on it (bg_analysis.h) ------------------------------------------------
+// d_played NULL: the search step.  Else the analysis of the played afterstates d_played [n][28]: the same stages with the played row
+// matched and forced into the kept set, and in place of the choice and the apply launch the per-lane results and their summary.
+static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, hipStream_t s)
 {
-    if (!env || top_k < 0) return BGAMD_E_INVALID;
-    HIPCHK(hipSetDevice(env->device));
     if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
     if (!env->net.has_weights[(flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0]) return BGAMD_E_NOWEIGHTS;
-    hipStream_t s = (hipStream_t)stream;
     const long long n = env->v.n;
     SearchState &se = env->srch;
+    AnalysisState &an = env->ana;
     int rc;
+    if (d_played) {
+        an.ready = false;
+        if (!an.summary && (rc = an.allocate(n))) return rc;
+    }
     if (!se.cnt) {
         uint32_t **per_game[] = {&se.cnt, &se.off, &se.fill, &se.kept, &se.koff};
         for (uint32_t **p : per_game) HIPCHK(hipMalloc(p, (size_t)(n + 1) * 4));
@@ -1857,7 +1886,8 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
                             {{(void **)&se.c_rows, 32}, {(void **)&se.c_key, 4}, {(void **)&se.c_v1, 4}, {(void **)&se.c_v2, 4},
                              {(void **)&se.c_rval, 4 * SRCH_ROLLS}});
     };
-    long long n_cand = top_k > 0 ? n * (long long)top_k : 0;         // bound on the kept candidates (top_k = 0: read back below)
+    // bound on the kept candidates (top_k = 0: read back below); the analysis keeps the played one beside the top_k
+    long long n_cand = top_k > 0 ? n * (long long)(top_k + (d_played ? 1 : 0)) : 0;
     if (top_k > 0 && (rc = grow_candidates(n_cand))) return rc;
     se.k = -1;
 
@@ -1877,8 +1907,14 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
     hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.cnt, se.off, n, (uint32_t *)nullptr);
     hipLaunchKernelGGL(srch_scatter_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, (const uint32_t *)se.off, se.fill, se.grp);
     const uint32_t k_lim = top_k > 0 ? (uint32_t)top_k : 0xFFFFFFFFu;
-    hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
-                       (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept);
+    if (d_played) {
+        hipLaunchKernelGGL(ana_match_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, env->v, flags, d_played, (const uint32_t *)se.cnt,
+                           (const uint32_t *)se.off, (const uint32_t *)se.grp, rows, info, an.v);
+        hipLaunchKernelGGL(ana_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                           (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept, an.v);
+    } else
+        hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                           (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept);
     hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.kept, se.koff, n, se.max);
     int K = top_k;
     if (top_k == 0) {                                  // every distinct afterstate: the list's length is read back (the one synchronisation)
@@ -1905,15 +1941,55 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
         if ((rc = score_virtual_lanes(env, run.slot, n_virtual, fanout, se.c_rval, s))) return rc;
     }
 
+    // stage D of the analysis: V2, the best and the played candidate's place, the summary -- nothing is applied
+    unsigned long long *scratch_err = env->scratch ? &env->scratch->v.counters[C_ERR] : (unsigned long long *)nullptr;
+    if (d_played) {
+        hipLaunchKernelGGL(ana_reduce_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                           (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
+                           (const float *)se.c_rval, se.c_v2, an.v, &env->v.counters[C_ERR], scratch_err);
+        hipLaunchKernelGGL(ana_summary_kernel<ANA_SUM_NT>, dim3(1), dim3(ANA_SUM_NT), 0, s, env->v, an.v, an.summary);
+        HIPCHK(hipGetLastError());
+        an.ready = true;
+        return BGAMD_OK;
+    }
     // stage D: V2, choice, and the greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice)
     hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
                        (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
-                       (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR],
-                       env->scratch ? &env->scratch->v.counters[C_ERR] : (unsigned long long *)nullptr);
+                       (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err);
     const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
     hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
     HIPCHK(hipGetLastError());
     se.k = K;
+    return BGAMD_OK;
+}
+
+int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
+{
+    if (!env || top_k < 0) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    return search_stages(env, flags, top_k, nullptr, (hipStream_t)stream);
+}
+
+// ---- move analysis (bg_analysis.h) -------------------------------------------------------------------------------------------------
+int bgamd_env_analyze_moves(bgamd_env *env, int flags, int top_k, const int32_t *d_played28, void *stream)
+{
+    if (!env || !d_played28 || top_k < 0 || (flags & ~(BGAMD_ONLY_P1 | BGAMD_ONLY_P2 | BGAMD_WEIGHTS_SLOT1))) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    return search_stages(env, flags, top_k, d_played28, (hipStream_t)stream);
+}
+
+int bgamd_env_analysis_read(bgamd_env *env, int32_t *d_status, int32_t *d_distinct, int32_t *d_rank1, int32_t *d_rank2,
+                            float *d_v1_played, float *d_v1_best, float *d_v2_played, float *d_v2_best, float *d_error,
+                            int32_t *d_best28, double *d_summary, void *stream)
+{
+    ENV_GUARD(env);
+    const AnalysisState &an = env->ana;
+    if (!an.ready) return BGAMD_E_INVALID;
+    const long long n = env->v.n;
+    const AnaView out{d_status, d_distinct, d_rank1, d_rank2, d_v1_played, d_v1_best, d_v2_played, d_v2_best, d_error, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(ana_read_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, (hipStream_t)stream, n, an.v,
+                       (const double *)an.summary, out, d_best28, d_summary);
+    HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
 

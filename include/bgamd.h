@@ -217,6 +217,51 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream);
  * the first search step. */
 int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream);
 
+/* ---- move analysis: a played move scored against the 2-ply search (GNU Backgammon's "analyse game") ----------------------------------
+ * Every lane's decision is its current board, side to move and dice as they stand (bgamd_env_set_states / bgamd_env_set_dice);
+ * d_played28[g] is the afterstate that was played from lane g (reference layout; the mover's turn bit is implied).  flags: only
+ * BGAMD_ONLY_P1, BGAMD_ONLY_P2 and BGAMD_WEIGHTS_SLOT1, with the greedy step's meaning.
+ *   1. stage A is the search's items 1-2 without the roll: the same roots, expansion and F32 incremental value net with the mover's turn
+ *      bit; v1(c) is the greedy step's value, bit for bit, a TERMINAL c scores its exact outcome; "distinct afterstates" and "smaller key"
+ *      mean what they mean there;
+ *   2. the distinct afterstates are ranked by (v1 for the mover, smaller key); kept are the top_k best (0 = all) AND the played afterstate,
+ *      wherever it ranks.  The kept list stays "best v1 first": a played candidate whose rank is >= top_k is its last entry.  The list is
+ *      bounded by n (top_k + 1) candidates up front: with top_k > 0 the host never waits (top_k = 0 reads the list's length back once);
+ *   3. V2 of every kept candidate exactly as the search's item 4: the same scoring passes on the search's scratch env and the same fp32
+ *      sum (doubles + 2 x others) / 36 in roll order.  A candidate's V2 depends on the candidate and the weights alone -- not on top_k,
+ *      the other lanes or the chunking;
+ *   4. nothing is applied: the lanes' boards, turns, dice, ply, episode and flags, bgamd_env_last_choice, the trajectory / ring logs and
+ *      the win / finished / steps counters are untouched.  candidates_raw, rows_evaluated and the node counters of bgamd_env_stats DO
+ *      advance, as stage A's launches advance them for any step.  The last search step's results are invalidated
+ *      (bgamd_env_search_read: BGAMD_E_INVALID until the next search step); the env's arenas are scratch, as for
+ *      bgamd_evaluate_incremental.
+ * Per lane (bgamd_env_analysis_read; any pointer may be NULL):
+ *   status    0 = analysed; 1 = the lane took no part (finished / frozen, or filtered out by BGAMD_ONLY_P1/P2); 2 = the mover has no legal
+ *             move (nothing to judge); 3 = `played` is not one of the lane's afterstates -- an illegal move, or a state with |count| > 15
+ *             or one that cannot be packed: it matches nothing and raises no error code.  (A doubles roll without a legal move is ONE
+ *             empty sequence, as everywhere: its only afterstate is the board itself, distinct = 1, and the board played is status 0.)
+ *   distinct  the number of distinct afterstates (status 0, 2, 3)
+ *   rank1     the number of distinct afterstates that beat the played one in the (v1, key) order: 0 = the played move is the 1-ply choice
+ *   v1_played / v1_best   v1 of the played afterstate / of rank 0
+ *   v2_played / v2_best   V2 of the played afterstate / the best V2 for the mover over the kept set (ties: the smaller key)
+ *   best28    the afterstate with v2_best
+ *   rank2     the number of kept candidates that beat the played one in the (V2 for the mover, smaller key) order
+ *   error     one fp32 subtraction, never negative: mover PLAYER1 v2_best - v2_played, mover PLAYER2 v2_played - v2_best; exactly 0.0 iff
+ *             the bits tie
+ * Status 3: the best side (distinct, v1_best, v2_best over the top_k, best28) is filled, every played-side field and error are 0 and
+ * rank1 = rank2 = -1.  Status 1 or 2: everything but status (and, for 2, distinct) is 0.
+ * d_summary[12] (doubles, the counts exact): for movers PLAYER1 [0..4] and PLAYER2 [5..9] the decisions analysed (status 0), the unforced
+ * ones (distinct >= 2), the mistakes (error > 0), the sum of (double) error, the largest error; [10] = lanes with status 2, [11] = with
+ * status 3.  Reduced in a fixed order without floating-point atomics: bit-identical from call to call, and each side's five numbers are
+ * the same whether the sides are analysed together or in BGAMD_ONLY_P1 and BGAMD_ONLY_P2 calls.
+ * Errors: BGAMD_E_INVALID for a NULL env or d_played28, top_k < 0, any other flag, a trajectory or ring log set (the search step's
+ * refusal), and for bgamd_env_analysis_read before the first analysis or after one that failed; BGAMD_E_NOWEIGHTS for an empty slot;
+ * arena and delta errors surface as they do for the search step.  Both calls are stream-ordered. */
+int bgamd_env_analyze_moves(bgamd_env *env, int flags, int top_k, const int32_t *d_played28 /*[n][28]*/, void *stream);
+int bgamd_env_analysis_read(bgamd_env *env, int32_t *d_status, int32_t *d_distinct, int32_t *d_rank1, int32_t *d_rank2,
+                            float *d_v1_played, float *d_v1_best, float *d_v2_played, float *d_v2_best, float *d_error,
+                            int32_t *d_best28 /*[n][28]*/, double *d_summary /*[12]*/, void *stream);
+
 /* ---- Monte Carlo rollouts (TD-Gammon / GNU Backgammon rollouts; points: see bgamd_env_rollout_outcomes_read) -----------------------
  * Plays T = trials games ("trials") from each of the P positions d_states28[P] / d_turn[P] (turn = side to move; d_turn NULL = PLAYER1)
  * with the greedy policy and reports how often PLAYER1 wins.  Trial i of position p is one game:
