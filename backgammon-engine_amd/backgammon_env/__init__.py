@@ -282,13 +282,26 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_run_greedy(self._h, self._flags(roll, auto_reset, False, only_player, slot),
                                                    float(epsilon), int(precision), int(n_steps), _stream()), "run_greedy")
 
-    def step_search(self, top_k=8, roll=True, auto_reset=True, no_flip=False, want_index=False, only_player=None, slot=0):
+    def step_search(self, top_k=8, roll=True, auto_reset=True, no_flip=False, want_index=False, only_player=None, slot=0, margin=None):
         """One 2-ply expectimax turn (include/bgamd.h, bgamd_env_step_search): the top_k best afterstates by the net (0 = all
         distinct ones) are re-scored by the average over the opponent's 21 rolls of the opponent's greedy reply, and the best of
-        them is played.  last_choice()["value"] is that 2-ply value; search_candidates() lists the kept candidates."""
-        _capi.check(self._lib.bgamd_env_step_search(self._h, self._flags(roll, auto_reset, no_flip, only_player, slot) |
-                                                    (WANT_INDEX if want_index else 0), int(top_k), _stream()), "step_search")
+        them is played.  last_choice()["value"] is that 2-ply value; search_candidates() lists the kept candidates.
+        margin (None = the step above): the filtered step (bgamd_env_step_search_filtered) -- only the candidates whose 1-ply value lies
+        within `margin` (>= 0, may be inf) of the best are searched, and a lane that keeps one candidate plays it unsearched (its value
+        and v2 are its 1-ply value).  Synchronises once."""
+        flags = self._flags(roll, auto_reset, no_flip, only_player, slot) | (WANT_INDEX if want_index else 0)
+        if margin is None:
+            _capi.check(self._lib.bgamd_env_step_search(self._h, flags, int(top_k), _stream()), "step_search")
+        else:
+            _capi.check(self._lib.bgamd_env_step_search_filtered(self._h, flags, int(top_k), float(margin), _stream()), "step_search_filtered")
         self._search_k = int(top_k)
+
+    def search_info(self):
+        """Host values of the last search step of either kind (bgamd_env_search_info; synchronises): [lanes that had a move, lanes
+        searched, kept candidates, virtual roots scored]."""
+        h = (C.c_int64 * 4)()
+        _capi.check(self._lib.bgamd_env_search_info(self._h, h), "search_info")
+        return list(h)
 
     def search_candidates(self):
         """The last search step's kept candidates, best 1-ply value first: (states[n,K,28], v1[n,K], v2[n,K], kept[n]); K is
@@ -341,7 +354,7 @@ class VecGame:
         return f, m
 
     def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
-                per_trial=False, variance_reduction=False, outcomes=False):
+                per_trial=False, variance_reduction=False, outcomes=False, plies=1, top_k=4, margin=float("inf")):
         """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
         move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
         trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
@@ -353,7 +366,16 @@ class VecGame:
         outcomes: also the games in points (bgamd_env_rollout_outcomes_read) -- counts [P, 6] (int64: trials that ended as PLAYER1 single
         game, gammon, backgammon, PLAYER2 single game, gammon, backgammon; truncated trials are in none), equity [P] and equity_stderr [P]
         (float64, PLAYER1's cubeless equity in points; a truncated trial counts 2 x - 1 of its net value x), with per_trial trial_points
-        [P, T] (int8, 0 = truncated).  The other outputs are the same as without it."""
+        [P, T] (int8, 0 = truncated).  The other outputs are the same as without it.
+        plies = 2: every turn of every trial is chosen by the filtered 2-ply search with (top_k, margin) instead of the greedy step
+        (bgamd_env_rollout_policy, set for this call; 1 is put back afterwards).  Same trials, same dice."""
+        if int(plies) != 1:
+            _capi.check(self._lib.bgamd_env_rollout_policy(self._h, int(plies), int(top_k), float(margin)), "rollout_policy")
+            try:
+                return self.rollout(states28, turn, trials, max_plies, rotate, seed, slot, position_offset, lanes, per_trial,
+                                    variance_reduction, outcomes)
+            finally:
+                _capi.check(self._lib.bgamd_env_rollout_policy(self._h, 1, 0, 0.0), "rollout_policy")
         st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
         P, T = st.shape[0], int(trials)
         t = self._dev(turn, torch.int32, (P,))

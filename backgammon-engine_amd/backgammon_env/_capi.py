@@ -63,11 +63,14 @@ SYMBOLS = [
     ("bgamd_env_last_choice", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_step_search", C.c_int, [_P, C.c_int, C.c_int, _P]),
     ("bgamd_env_search_read", C.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("bgamd_env_step_search_filtered", C.c_int, [_P, C.c_int, C.c_int, C.c_float, _P]),
+    ("bgamd_env_search_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("bgamd_env_analyze_moves", C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     ("bgamd_env_analysis_read", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_rollout", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
                                     _P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_rollout_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("bgamd_env_rollout_policy", C.c_int, [_P, C.c_int, C.c_int, C.c_float]),
     ("bgamd_env_evaluate_preroll", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, _P]),
     ("bgamd_env_rollout_vr_read", C.c_int, [_P, _P, _P, _P, _P]),
     ("bgamd_outcomes", C.c_int, [_P, C.c_int64, _P, _P]),

@@ -7,7 +7,8 @@ import math
 import numpy as np
 
 
-def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, seed=20240603, variance_reduction=False, outcomes=False):
+def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, seed=20240603, variance_reduction=False, outcomes=False,
+                  plies=1, rollout_top_k=4, rollout_margin=float("inf")):
     """Rolls out the candidates a 2-ply search keeps for one turn and ranks them by rollout.
 
     env: a one-lane VecGame with weights in slot 0.  Its lane is set to the position and searched; its board, turn and dice are
@@ -23,7 +24,9 @@ def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, s
     ranked by vr_mean instead.
     outcomes: every candidate also carries equity, equity_stderr (PLAYER1's cubeless equity in points: gammons 2, backgammons 3) and
     counts (trials that ended as PLAYER1 single game, gammon, backgammon, PLAYER2 single game, gammon, backgammon).  The ranking does
-    not change: it stays by mean (or vr_mean), the share of wins."""
+    not change: it stays by mean (or vr_mean), the share of wins.
+    plies = 2: the trials are played by the filtered 2-ply search with (rollout_top_k, rollout_margin) instead of the greedy step
+    (VecGame.rollout(plies=2)): "roll it out at 2 plies"."""
     if env.n != 1:
         raise ValueError("rollout_moves needs a one-lane VecGame")
     mover = int(turn)
@@ -45,7 +48,8 @@ def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, s
         after = cst[0, k]
         idx = int(np.flatnonzero((st == after).all(axis=1))[0])
         r = env.rollout(after[None], [1 - mover], trials, max_plies=max_plies, rotate=True, seed=seed,
-                        variance_reduction=variance_reduction, outcomes=outcomes)
+                        variance_reduction=variance_reduction, outcomes=outcomes, plies=plies, top_k=rollout_top_k,
+                        margin=rollout_margin)
         out.append({"index": idx, "seq": [tuple(int(x) for x in sq[idx, m]) for m in range(int(ln[idx]))], "state": after,
                     "v1": float(v1[0, k]), "v2": float(v2[0, k]), "mean": float(r["mean"][0]), "stderr": float(r["stderr"][0]),
                     "turns": int(r["turns"][0])})

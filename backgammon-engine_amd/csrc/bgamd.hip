@@ -643,6 +643,7 @@ __global__ void legal_moves_kernel(EnvView e, const int32_t *__restrict__ player
 #include "bg_vr.h"
 #include "bg_health.h"
 #include "bg_analysis.h"
+#include "bg_filter.h"
 
 }  // namespace
 
@@ -742,7 +743,16 @@ struct SearchState {
     float *c_v1 = nullptr, *c_v2 = nullptr, *c_rval = nullptr;     // c_rval [c_cap][21]
     long long c_cap = 0;
     int k = -1;                            // K of the last search step (-1: none yet)
-    void release() { free_all({cnt, off, fill, kept, koff, max, grp, rank, c_rows, c_key, c_v1, c_v2, c_rval}); *this = SearchState{}; }
+    // the filtered step (bg_filter.h): skept [n] = kept of the searched lanes (kept >= 2, else 0), soff [n + 1] its scan, vmap [c_cap] the
+    // searched candidates' places in the candidate list; bgamd_env_search_info: d_info [4], the least kept count of a searched lane and
+    // the stream of the last search step, the host copy once it has been read
+    uint32_t *skept = nullptr, *soff = nullptr, *vmap = nullptr;
+    unsigned long long *d_info = nullptr;
+    uint32_t min_searched = 1;
+    hipStream_t stream = nullptr;
+    bool info_read = false;
+    int64_t info[4] = {0, 0, 0, 0};
+    void release() { free_all({cnt, off, fill, kept, koff, max, grp, rank, c_rows, c_key, c_v1, c_v2, c_rval, skept, soff, vmap, d_info}); *this = SearchState{}; }
 };
 
 // move analysis (bgamd_env_analyze_moves, bg_analysis.h): the per-lane results of the last one and its summary
@@ -861,6 +871,8 @@ struct bgamd_env {
     // whole number of 16-byte units, so that the rollout's one fill launch clears both.  48 bytes, allocated with every env (env_allocate).
     unsigned long long *a_ctr = nullptr;
     SearchState srch;
+    int ro_plies = 1, ro_top_k = 0;        // bgamd_env_rollout_policy: who plays the trials' turns (1 = the greedy step)
+    float ro_margin = 0.0f;
     AnalysisState ana;
     RolloutState ro;
     PrerollState pre;
@@ -1860,9 +1872,22 @@ static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int
 }
 
 // ---- 2-ply expectimax (bg_search.h) and the move analysis built on it (bg_analysis.h) ------------------------------------------------
+// The filtered step's kernels (bg_filter.h) are launched through these; they are DEFINED at the end of this file.  A kernel template's code
+// is emitted where the file first launches it, so launches written here would push the template kernels that follow (the pre-roll,
+// outcome, analysis-read and learner kernels) to other addresses; launched from the end of the file, the new code lies behind all of it.
+static void launch_flt_select(hipStream_t s, long long n, const SearchState &se, const uint4 *rows, const uint2 *info, const float *values,
+                              uint32_t k_lim, float margin);
+static void launch_flt_vmap(hipStream_t s, long long n, const SearchState &se);
+static void launch_flt_fanout(hipStream_t s, const EnvView &lanes, long long v0, long long n, const SearchState &se);
+static void launch_flt_reduce(hipStream_t s, long long n, const SearchState &se, unsigned long long *best, unsigned long long *err,
+                              unsigned long long *scratch_err);
+static void launch_flt_info(hipStream_t s, long long n, const SearchState &se);
+
 // d_played NULL: the search step.  Else the analysis of the played afterstates d_played [n][28]: the same stages with the played row
 // matched and forced into the kept set, and in place of the choice and the apply launch the per-lane results and their summary.
-static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, hipStream_t s)
+// margin NULL: every candidate of the top_k is searched, as ever.  Else the filtered step (bg_filter.h, search step only): the margin
+// rule in the selection, no virtual root for a lane that keeps one candidate, and scoring passes for the list's real length.
+static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, const float *margin, hipStream_t s)
 {
     if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
     if (!env->net.has_weights[(flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0]) return BGAMD_E_NOWEIGHTS;
@@ -1875,20 +1900,21 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
         if (!an.summary && (rc = an.allocate(n))) return rc;
     }
     if (!se.cnt) {
-        uint32_t **per_game[] = {&se.cnt, &se.off, &se.fill, &se.kept, &se.koff};
+        uint32_t **per_game[] = {&se.cnt, &se.off, &se.fill, &se.kept, &se.koff, &se.skept, &se.soff};
         for (uint32_t **p : per_game) HIPCHK(hipMalloc(p, (size_t)(n + 1) * 4));
         HIPCHK(hipMalloc(&se.max, 8));
+        HIPCHK(hipMalloc(&se.d_info, 4 * 8));
         HIPCHK(hipMalloc(&se.grp, (size_t)env->sv.cap_rows * 4));
         HIPCHK(hipMalloc(&se.rank, (size_t)env->sv.cap_rows * 4));
     }
     auto grow_candidates = [&](long long need) {       // (at least 1 024 rows once there is one)
         return grow_buffers(need > 0 && need < 1024 ? 1024 : need, se.c_cap,
                             {{(void **)&se.c_rows, 32}, {(void **)&se.c_key, 4}, {(void **)&se.c_v1, 4}, {(void **)&se.c_v2, 4},
-                             {(void **)&se.c_rval, 4 * SRCH_ROLLS}});
+                             {(void **)&se.c_rval, 4 * SRCH_ROLLS}, {(void **)&se.vmap, 4}});
     };
     // bound on the kept candidates (top_k = 0: read back below); the analysis keeps the played one beside the top_k
-    long long n_cand = top_k > 0 ? n * (long long)(top_k + (d_played ? 1 : 0)) : 0;
-    if (top_k > 0 && (rc = grow_candidates(n_cand))) return rc;
+    long long n_cand = top_k > 0 && !margin ? n * (long long)(top_k + (d_played ? 1 : 0)) : 0;
+    if (n_cand > 0 && (rc = grow_candidates(n_cand))) return rc;
     se.k = -1;
 
     // stage A: the greedy step's roots, expansion and incremental value net, no apply
@@ -1912,12 +1938,25 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
                            (const uint32_t *)se.off, (const uint32_t *)se.grp, rows, info, an.v);
         hipLaunchKernelGGL(ana_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
                            (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept, an.v);
-    } else
+    } else if (margin)
+        launch_flt_select(s, n, se, rows, info, (const float *)env->v.values, k_lim, *margin);
+    else
         hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
                            (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept);
     hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.kept, se.koff, n, se.max);
     int K = top_k;
-    if (top_k == 0) {                                  // every distinct afterstate: the list's length is read back (the one synchronisation)
+    long long n_searched = 0;                          // filtered step: the searched candidates (those of the lanes that kept >= 2)
+    if (margin) {                                      // the lengths of both lists are read back (the one synchronisation)
+        hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.skept, se.soff, n, (uint32_t *)nullptr);
+        uint32_t h[3] = {0, 0, 0};
+        HIPCHK(hipMemcpyAsync(&h[0], se.koff + n, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h[1], se.max, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h[2], se.soff + n, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        n_cand = h[0]; n_searched = h[2];
+        if (top_k == 0) K = (int)h[1];
+        if ((rc = grow_candidates(n_cand))) return rc;
+    } else if (top_k == 0) {                                  // every distinct afterstate: the list's length is read back (the one synchronisation)
         uint32_t h[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(&h[0], se.koff + n, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&h[1], se.max, 4, hipMemcpyDeviceToHost, s));
@@ -1931,8 +1970,13 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
                        (const uint32_t *)se.koff, se.c_rows, se.c_key, se.c_v1);
 
     // stage C: one virtual lane per (candidate, opponent roll), scored on the scratch env
-    const long long n_virtual = n_cand * SRCH_ROLLS;
-    if (n_virtual > 0) {
+    const long long n_virtual = (margin ? n_searched : n_cand) * SRCH_ROLLS;
+    if (margin && n_virtual > 0) {
+        launch_flt_vmap(s, n, se);
+        if ((rc = scratch_env(env, &env->scratch, search_lanes(n_virtual), false, 0, s))) return rc;
+        const auto fanout = [&](const EnvView &lanes, long long v0) { launch_flt_fanout(s, lanes, v0, n, se); };
+        if ((rc = score_virtual_lanes(env, run.slot, n_virtual, fanout, se.c_rval, s))) return rc;
+    } else if (n_virtual > 0) {
         if ((rc = scratch_env(env, &env->scratch, search_lanes(n_virtual), false, 0, s))) return rc;
         const auto fanout = [&](const EnvView &lanes, long long v0) {
             hipLaunchKernelGGL(srch_fanout_kernel, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.koff + n),
@@ -1953,13 +1997,19 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
         return BGAMD_OK;
     }
     // stage D: V2, choice, and the greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice)
-    hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
-                       (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
-                       (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err);
+    if (margin)
+        launch_flt_reduce(s, n, se, env->sv.best, &env->v.counters[C_ERR], scratch_err);
+    else
+        hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                           (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
+                           (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err);
     const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
     hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
     HIPCHK(hipGetLastError());
     se.k = K;
+    se.min_searched = margin ? 2u : 1u;
+    se.stream = s;
+    se.info_read = false;
     return BGAMD_OK;
 }
 
@@ -1967,7 +2017,32 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
 {
     if (!env || top_k < 0) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
-    return search_stages(env, flags, top_k, nullptr, (hipStream_t)stream);
+    return search_stages(env, flags, top_k, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int bgamd_env_step_search_filtered(bgamd_env *env, int flags, int top_k, float margin, void *stream)
+{
+    if (!env || top_k < 0 || !(margin >= 0.0f)) return BGAMD_E_INVALID;      // (a NaN margin fails the comparison)
+    HIPCHK(hipSetDevice(env->device));
+    return search_stages(env, flags, top_k, nullptr, &margin, (hipStream_t)stream);
+}
+
+// The counts are taken when they are asked for, on the stream of the step they describe: a search step launches nothing for them.
+int bgamd_env_search_info(bgamd_env *env, int64_t h_out[4])
+{
+    ENV_GUARD(env);
+    SearchState &se = env->srch;
+    if (!h_out || se.k < 0) return BGAMD_E_INVALID;
+    if (!se.info_read) {
+        unsigned long long h[4] = {0, 0, 0, 0};
+        launch_flt_info(se.stream, env->v.n, se);
+        HIPCHK(hipMemcpyAsync(h, se.d_info, 4 * 8, hipMemcpyDeviceToHost, se.stream));
+        HIPCHK(hipStreamSynchronize(se.stream));
+        for (int q = 0; q < 4; ++q) se.info[q] = (int64_t)h[q];
+        se.info_read = true;
+    }
+    for (int q = 0; q < 4; ++q) h_out[q] = se.info[q];
+    return BGAMD_OK;
 }
 
 // ---- move analysis (bg_analysis.h) -------------------------------------------------------------------------------------------------
@@ -1975,7 +2050,7 @@ int bgamd_env_analyze_moves(bgamd_env *env, int flags, int top_k, const int32_t 
 {
     if (!env || !d_played28 || top_k < 0 || (flags & ~(BGAMD_ONLY_P1 | BGAMD_ONLY_P2 | BGAMD_WEIGHTS_SLOT1))) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
-    return search_stages(env, flags, top_k, d_played28, (hipStream_t)stream);
+    return search_stages(env, flags, top_k, d_played28, nullptr, (hipStream_t)stream);
 }
 
 int bgamd_env_analysis_read(bgamd_env *env, int32_t *d_status, int32_t *d_distinct, int32_t *d_rank1, int32_t *d_rank2,
@@ -2121,11 +2196,28 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     const StepStreams ss{s, sc->overlap ? sc->side : s, sc->n_cu};
     long long steps = 0;
 
+    // plies = 2 (bgamd_env_rollout_policy): every turn is one filtered search step of the trial env.  Its virtual roots are scored on
+    // THIS env's scratch env, lent to the trial env for the step: the luck pass uses the same one between the steps (everything is
+    // stream-ordered), and a second env of up to SEARCH_CHUNK lanes (~3.4 GB) would buy nothing.  It is sized once, for top_k (8 when
+    // there is no limit) candidates per lane, so that a turn with many candidates does not re-create it; the search's per-lane and
+    // candidate buffers of the trial env come to ~0.2 GB at 65 536 lanes and top_k 5 (2 x 67 MB of row indices and ranks, 43 MB of candidates).
+    const bool two_ply = env->ro_plies == 2;
+    const int pol_k = env->ro_top_k;
+    const float pol_margin = env->ro_margin;
+    if (two_ply && (rc = scratch_env(env, &env->scratch, search_lanes(L * (long long)(pol_k > 0 ? pol_k : 8) * SRCH_ROLLS), false, 0, s))) return rc;
+    auto search_turn = [&](int fl) -> int {
+        sc->scratch = env->scratch;
+        const int e = search_stages(sc, fl, pol_k, nullptr, &pol_margin, s);
+        env->scratch = sc->scratch;                    // (re-created if it had to grow)
+        sc->scratch = nullptr;
+        return e;
+    };
+
     // rotation: the first turn of every (position, ordered pair) as one greedy step with injected dice, L virtual lanes at a time
     if (rotate) {
         for (long long v0 = 0; v0 < n_fan; v0 += L) {
             hipLaunchKernelGGL(ro_fan_seed_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, r);
-            if ((rc = bgamd_env_step_greedy(sc, run_flags, 0.0f, BGAMD_F32, s))) return rc;
+            if ((rc = two_ply ? search_turn(run_flags) : bgamd_env_step_greedy(sc, run_flags, 0.0f, BGAMD_F32, s))) return rc;
             hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, ro.fan);
             ++steps;
         }
@@ -2159,6 +2251,7 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
         R = D < 1 ? 1 : (int)(D < ROLLOUT_RUN ? D : ROLLOUT_RUN);
         while (D > 0 && D % R) --R;
     }
+    if (two_ply) R = 1;                                // a search turn is a step of its own: a refill after every turn
     const int G = R >= 16 ? 1 : 16 / R;                // runs between two reads of the trials-done counter (~16 turns)
     auto refill = [&]() -> int {
         hipLaunchKernelGGL(ro_refill_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, r);
@@ -2198,6 +2291,14 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
                 if (stalled > (long long)RO_TURN_LIMIT + 64) return BGAMD_E_INVALID;      // (cannot happen: the kernels' own limit fires first)
             }
             for (int gi = 0; gi < G; ++gi) {
+                if (two_ply) {
+                    // the turn's dice go into the lanes first (the TURN-stream dice of the lane's game id and ply, what BGAMD_ROLL draws):
+                    // the luck pass reads them, and the search step plays them as set dice -- with and without the luck pass
+                    hipLaunchKernelGGL(dice_kernel, grid1(L, 256), dim3(256), 0, s, sc->v, (const int32_t *)nullptr, (int32_t *)nullptr, 1);
+                    if ((vr && (e = vr_turn())) || (e = search_turn(run_flags)) || (e = refill())) return e;
+                    steps += 1;
+                    continue;
+                }
                 GreedyRun run;
                 if ((e = run.init(sc, BGAMD_ROLL | run_flags, 0.0f, BGAMD_F32)) || (e = run.begin(s))) return e;
                 for (int t = 0; t < R; ++t)
@@ -2225,6 +2326,13 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     HIPCHK(hipStreamSynchronize(s));
     if (vr) { ro.vr_P = P; ro.vr_T = T; }
     ro.out_P = P; ro.out_T = T;
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_policy(bgamd_env *env, int plies, int top_k, float margin)
+{
+    if (!env || (plies != 1 && plies != 2) || top_k < 0 || !(margin >= 0.0f)) return BGAMD_E_INVALID;
+    env->ro_plies = plies; env->ro_top_k = top_k; env->ro_margin = margin;
     return BGAMD_OK;
 }
 
@@ -3317,3 +3425,37 @@ int bgamd_td_replay_allreduce(bgamd_td *td, int64_t n_steps, const int64_t *h_n_
 }
 
 }  // extern "C"
+
+// ---- the filtered search step's launches (declared before search_stages: why they stand here is said there) ---------------------------
+static void launch_flt_select(hipStream_t s, long long n, const SearchState &se, const uint4 *rows, const uint2 *info, const float *values,
+                              uint32_t k_lim, float margin)
+{
+    hipLaunchKernelGGL(flt_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                       (const uint32_t *)se.grp, rows, info, values, k_lim, margin, se.rank, se.kept, se.skept);
+}
+
+static void launch_flt_vmap(hipStream_t s, long long n, const SearchState &se)
+{
+    hipLaunchKernelGGL(flt_vmap_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                       (const uint32_t *)se.koff, (const uint32_t *)se.soff, se.vmap);
+}
+
+static void launch_flt_fanout(hipStream_t s, const EnvView &lanes, long long v0, long long n, const SearchState &se)
+{
+    hipLaunchKernelGGL(flt_fanout_kernel<SRCH_NT>, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.soff + n),
+                       (const uint32_t *)se.vmap, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
+}
+
+static void launch_flt_reduce(hipStream_t s, long long n, const SearchState &se, unsigned long long *best, unsigned long long *err,
+                              unsigned long long *scratch_err)
+{
+    hipLaunchKernelGGL(flt_reduce_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                       (const uint32_t *)se.koff, (const uint32_t *)se.soff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key,
+                       (const float *)se.c_v1, (const float *)se.c_rval, se.c_v2, best, err, scratch_err);
+}
+
+static void launch_flt_info(hipStream_t s, long long n, const SearchState &se)
+{
+    hipLaunchKernelGGL(flt_info_kernel<1024>, dim3(1), dim3(1024), 0, s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff,
+                       (const uint32_t *)se.c_key, se.min_searched, se.d_info);
+}

@@ -217,6 +217,33 @@ int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream);
  * the first search step. */
 int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, float *d_v2, int32_t *d_kept, void *stream);
 
+/* ---- the filtered search step (GNU Backgammon's move filter) -------------------------------------------------------------------------
+ * bgamd_env_step_search (items 1-6 above, the same flags, refusals and errors) with these differences:
+ *   - margin: with d(c) = v1(rank 0) - v1(c) for mover PLAYER1 and v1(c) - v1(rank 0) for mover PLAYER2 -- ONE fp32 subtraction, never
+ *     negative -- a distinct afterstate is kept iff its rank in the (v1 for the mover, smaller key) order is below top_k (0 = no limit)
+ *     AND d(c) <= margin.  Rank 0 is always kept.  Terminal candidates take part with their exact outcome, as they do in item 2.  margin
+ *     is >= 0 and may be +inf; NaN or a negative margin: BGAMD_E_INVALID.  The kept list stays "best v1 first";
+ *   - singletons: a lane with ONE kept candidate -- a forced move, or a lane the filter cut to one -- is not searched.  It contributes no
+ *     virtual root, its candidate is played, bgamd_env_last_choice reports its v1 as the value and bgamd_env_search_read v2 = v1 for it.
+ *     With margin = +inf the step therefore equals bgamd_env_step_search except for the reported value and v2 of such lanes: their
+ *     choice and every board are the same;
+ *   - list length: the step reads the real lengths of the candidate list and of the searched candidates back once (it SYNCHRONISES the
+ *     stream once, as top_k = 0 does for bgamd_env_step_search) and launches only the scoring passes the searched list needs;
+ *   - V2 of a kept candidate of a searched lane depends on the candidate and the weights alone -- not on top_k, the margin, the other
+ *     lanes or the chunking.
+ * bgamd_env_search_read works after either kind of step. */
+int bgamd_env_step_search_filtered(bgamd_env *env, int flags, int top_k, float margin, void *stream);
+/* Host values of the last search step of either kind (BGAMD_E_INVALID before the first, and after an analysis, as bgamd_env_search_read):
+ *   h_out[0] lanes that had a move (kept >= 1);
+ *   h_out[1] lanes searched: kept >= 2 after a filtered step; after bgamd_env_step_search every lane that had a move (= h_out[0]: it
+ *            searches its singletons too);
+ *   h_out[2] kept candidates;
+ *   h_out[3] virtual roots scored = 21 x the non-terminal kept candidates of the searched lanes (the virtual lanes under a terminal
+ *            candidate, and bgamd_env_step_search's slots past a lane's kept count, are finished lanes and are not counted).
+ * The counts are taken when asked for (one small launch on the step's stream, which is SYNCHRONISED; further calls return the same
+ * values without a launch): a search step launches nothing for them. */
+int bgamd_env_search_info(bgamd_env *env, int64_t h_out[4]);
+
 /* ---- move analysis: a played move scored against the 2-ply search (GNU Backgammon's "analyse game") ----------------------------------
  * Every lane's decision is its current board, side to move and dice as they stand (bgamd_env_set_states / bgamd_env_set_dice);
  * d_played28[g] is the afterstate that was played from lane g (reference layout; the mover's turn bit is implied).  flags: only
@@ -297,6 +324,20 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
 /* Diagnostics of the last rollout (host values): h_out = [lanes, env steps issued (rotation steps included), lane-steps that played a
  * turn of a live trial, turns per run between refill points].  Idle share = 1 - h_out[2] / (h_out[0] h_out[1]). */
 int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4]);
+/* Who plays the turns of bgamd_env_rollout's trials.  The setting sticks to the env.  plies = 1 (the default): the greedy step, as described
+ * above -- launches and outputs are what they are on an env that never called this.  plies = 2: every turn of every trial, the rotated
+ * first turn included, is chosen by bgamd_env_step_search_filtered with (top_k, margin) and the rollout's weight slot.  Everything else in
+ * the rollout's contract stays: trial ids and TURN-stream dice (a 2-ply rollout shares its dice with the 1-ply rollout of the same
+ * positions, T and seed), the rotation pairs, a pass is a turn, the outcome scoring, truncation at max_plies by the fp32 net value of the
+ * board reached, the fixed reduction order, independence of `lanes`, of the call order and of position_offset splits, no side effect on
+ * the env.  Each search turn is a step of its own with a refill after it: bgamd_env_rollout_info reports 1 turn per run.
+ * bgamd_env_rollout_outcomes_read works as before.  BGAMD_ROLLOUT_VR is allowed: a turn's luck keeps its definition (the 1-ply f and mean
+ * of bgamd_env_evaluate_preroll; E[luck | history] = 0 whatever the policy, so the adjusted value stays unbiased) and the plain outputs
+ * are bit-identical with and without the flag.
+ * The virtual roots are scored on THIS env's search scratch env (shared with the luck pass; at most 131 072 lanes, ~3.4 GB); the trial
+ * env's own search buffers add ~0.2 GB at 65 536 lanes and top_k 5.
+ * plies other than 1 or 2, top_k < 0, a negative or NaN margin: BGAMD_E_INVALID (the setting is unchanged). */
+int bgamd_env_rollout_policy(bgamd_env *env, int plies /* 1 | 2 */, int top_k, float margin);
 
 /* ---- 1-ply pre-roll evaluation (GNU Backgammon's "evaluation before the roll") ------------------------------------------------------
  * For each of the n positions s = d_states28[n] with the side to roll m = d_turn[n] (NULL = PLAYER1), what the roller can expect from

@@ -11,7 +11,10 @@ median ratio; 1 for the plain call).
 
 --outcomes: the same run with the games read in points after every call (bgamd_env_rollout_outcomes_read, inside the timed region):
 every record also carries the six shares (PLAYER1 single game / gammon / backgammon, PLAYER2 the same) over the finished trials of all
-positions and the mean equity of the positions in points."""
+positions and the mean equity of the positions in points.
+
+--plies 2 [--top-k K --margin M]: the trials are played by the filtered 2-ply search (bgamd_env_rollout_policy) instead of the greedy
+step; a 2-ply turn costs ~100 greedy steps, so give fewer --trials.  With --vr: the luck pass beside 2-ply turns."""
 import argparse
 import json
 import os
@@ -26,6 +29,9 @@ for p in (ROOT, os.path.join(ROOT, "backgammon-engine_amd")):
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+
+POLICY = {}                                            # --plies 2: the rollout policy every call is given
 
 
 def _greedy_ms(env, steps, regions):
@@ -64,7 +70,13 @@ def main():
     ap.add_argument("--vr", action="store_true", help="luck-adjusted rollouts against plain ones")
     ap.add_argument("--vr-trials", type=int, default=2592)
     ap.add_argument("--outcomes", action="store_true", help="also read gammons / backgammons and the equity in points")
+    ap.add_argument("--plies", type=int, default=1, choices=(1, 2), help="who plays the trials: 1 = the greedy step, 2 = the filtered 2-ply search")
+    ap.add_argument("--top-k", type=int, default=5, help="--plies 2: the search's top_k")
+    ap.add_argument("--margin", type=float, default=0.04, help="--plies 2: the search's margin")
+    ap.add_argument("--configs", default="full,truncated,pair", help="which of full (M = 0), truncated (M = 7), pair (M = 0 again) to run")
     a = ap.parse_args()
+    global POLICY
+    POLICY = dict(plies=2, top_k=a.top_k, margin=a.margin) if a.plies == 2 else {}
     if a.vr and a.outcomes:
         ap.error("--outcomes reads the plain run's games; it is not combined with --vr")
     import backgammon_env as bg
@@ -79,13 +91,14 @@ def main():
         env.close()
         return
     out = []
-    for name, M in (("full", 0), ("truncated", 7), ("truncated", 0)):
-        env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes)       # warm-up (scratch env, buffers)
+    configs = {"full": ("full", 0), "truncated": ("truncated", 7), "pair": ("truncated", 0)}
+    for name, M in [configs[c] for c in a.configs.split(",")]:
+        env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes, **POLICY)       # warm-up (scratch env, buffers)
         ms = []
         for _ in range(a.regions):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            r = env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes, outcomes=a.outcomes)
+            r = env.rollout(st, tu, a.trials, max_plies=M, rotate=True, seed=5, lanes=a.lanes, outcomes=a.outcomes, **POLICY)
             if a.outcomes:
                 torch.cuda.synchronize()                           # (the read is stream-ordered after the call)
             ms.append((time.perf_counter() - t0) * 1e3)            # (the call synchronises)
@@ -94,7 +107,7 @@ def main():
         n_trials = a.positions * a.trials
         turns = int(r["turns"].sum())
         idle = 1.0 - info[2] / float(info[0] * info[1])
-        rec = {"config": name, "max_plies": M, "lanes": info[0], "positions": a.positions, "trials": a.trials, "ms": round(m, 2),
+        rec = {"config": name, "max_plies": M, "plies": a.plies, "lanes": info[0], "positions": a.positions, "trials": a.trials, "ms": round(m, 2),
                "trials_per_s": round(n_trials / m * 1e3), "trial_turns_per_s": round(turns / m * 1e3),
                "greedy_env_steps_per_s": round(greedy_sps), "ratio_to_greedy": round(turns / m * 1e3 / greedy_sps, 3),
                "idle_share": round(idle, 4), "env_steps": info[1], "turns_per_run": info[3], "mean_turns": round(turns / n_trials, 2),
@@ -112,12 +125,12 @@ def main():
 
 
 def _timed(env, st, tu, trials, M, lanes, regions, vr):
-    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr)      # warm-up
+    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, **POLICY)      # warm-up
     ms = []
     for _ in range(regions):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr)
+        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, **POLICY)
         ms.append((time.perf_counter() - t0) * 1e3)                # (the call synchronises; vr_read is stream-ordered after it)
     torch.cuda.synchronize()
     return statistics.median(ms), r, ms
@@ -125,7 +138,7 @@ def _timed(env, st, tu, trials, M, lanes, regions, vr):
 
 def _vr(env, st, tu, a, greedy_sps):
     out = []
-    for name, M in (("full", 0), ("truncated", 7)):
+    for name, M in [c for c in (("full", 0), ("truncated", 7)) if c[0] in a.configs.split(",")]:
         ms_p, rp, _ = _timed(env, st, tu, a.vr_trials, M, a.lanes, a.regions, False)
         ms_v, rv, regions = _timed(env, st, tu, a.vr_trials, M, a.lanes, a.regions, True)
         info = env.rollout_info()
@@ -136,7 +149,7 @@ def _vr(env, st, tu, a, greedy_sps):
         n_trials = a.positions * a.vr_trials
         turns = int(rp["turns"].sum())
         roots = 21 * turns
-        rec = {"config": name, "max_plies": M, "lanes": info[0], "positions": a.positions, "trials": a.vr_trials,
+        rec = {"config": name, "max_plies": M, "plies": a.plies, "lanes": info[0], "positions": a.positions, "trials": a.vr_trials,
                "plain_ms": round(ms_p, 2), "vr_ms": round(ms_v, 2), "cost_ratio": round(ms_v / ms_p, 2),
                "vr_virtual_roots_per_s": round(roots / (ms_v - ms_p) * 1e3),
                "greedy_env_steps_per_s": round(greedy_sps), "vr_roots_to_greedy": round(roots / (ms_v - ms_p) * 1e3 / greedy_sps, 3),

@@ -1,6 +1,10 @@
 """Throughput of the 2-ply expectimax step (bgamd_env_step_search): searched moves/s and virtual roots/s at several env sizes and
 top_k, set against the greedy step's env steps/s measured in the same run.  Every figure is the median of several timed regions
-after a warm-up (HIP events around `--steps` back-to-back steps).  One JSON line per configuration, then a summary line."""
+after a warm-up (HIP events around `--steps` back-to-back steps).  One JSON line per configuration, then a summary line.
+
+--margin M[,M...]: after each unfiltered configuration, the filtered step (bgamd_env_step_search_filtered) with each margin from the same
+starting positions: ms per step, the virtual roots scored, the lanes searched and the kept candidates of the last step
+(bgamd_env_search_info), and the share of lanes whose choice differs from the unfiltered step's on one common set of positions and dice."""
 import argparse
 import json
 import os
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--regions", type=int, default=5)
+    ap.add_argument("--margin", default="", help="comma-separated margins of the filtered step (none: the unfiltered step only)")
     a = ap.parse_args()
     import backgammon_env as bg
     w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
@@ -59,6 +64,28 @@ def main():
                  "regions_ms": [round(x, 4) for x in all_ms]}
             print(json.dumps(r), flush=True)
             out.append(r)
+            for mg in [float(x) for x in a.margin.split(",") if x]:
+                env.reset()
+                env.run_greedy(10)
+                f_ms, f_all = _time(lambda: env.step_search(top_k=k, margin=mg), a.steps, a.warmup, a.regions)
+                info = env.search_info()
+                # the choices of both steps on one set of positions and dice (nothing flips or restarts: the boards are the choices)
+                env.reset()
+                env.run_greedy(10)
+                env.roll()
+                st, tu, dice = env.states().clone(), env.turns().clone(), env.dice().clone()
+                env.step_search(top_k=k, roll=False, auto_reset=False, no_flip=True)
+                plain = env.states().clone()
+                env.set_states(st, tu)
+                env.set_dice(dice)
+                env.step_search(top_k=k, roll=False, auto_reset=False, no_flip=True, margin=mg)
+                differs = float((env.states() != plain).any(1).float().mean())
+                r = {"n": n, "top_k": k, "margin": mg, "ms_per_search_step": round(f_ms, 4), "unfiltered_ms_per_search_step": round(ms, 4),
+                     "speedup": round(ms / f_ms, 2), "lanes_with_a_move": info[0], "lanes_searched": info[1], "kept_candidates": info[2],
+                     "virtual_roots_last_step": info[3], "choice_differs_share": round(differs, 5),
+                     "regions_ms": [round(x, 4) for x in f_all]}
+                print(json.dumps(r), flush=True)
+                out.append(r)
         env.close()
     print(json.dumps({"search_bench": out}))
 
