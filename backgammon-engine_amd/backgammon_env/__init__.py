@@ -282,6 +282,28 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_run_greedy(self._h, self._flags(roll, auto_reset, False, only_player, slot),
                                                    float(epsilon), int(precision), int(n_steps), _stream()), "run_greedy")
 
+    def step_sampled(self, temperature, roll=True, auto_reset=True, precision=F32, no_flip=False, want_index=False, only_player=None,
+                     slot=0):
+        """A greedy step in which every lane plays an afterstate drawn with probability ~ exp(value for the mover / temperature) over the
+        distinct afterstates the net scored (include/bgamd.h, bgamd_env_step_sampled: Gumbel-max, noise keyed by seed, game id, ply and
+        the afterstate).  temperature 0 is step_greedy, bit for bit; negative, NaN or inf raises.  last_choice() reports the sampled
+        move and its value; the other arguments mean what they mean for step_greedy."""
+        _capi.check(self._lib.bgamd_env_step_sampled(self._h, self._flags(roll, auto_reset, no_flip, only_player, slot) |
+                                                     (WANT_INDEX if want_index else 0), float(temperature), int(precision), _stream()),
+                    "step_sampled")
+
+    def run_sampled(self, n_steps, temperature, roll=True, auto_reset=True, precision=F32, only_player=None, slot=0):
+        """n_steps sampled steps in one call: the same games as n_steps calls of step_sampled (run_greedy's fused step boundary)."""
+        _capi.check(self._lib.bgamd_env_run_sampled(self._h, self._flags(roll, auto_reset, False, only_player, slot), float(temperature),
+                                                    int(precision), int(n_steps), _stream()), "run_sampled")
+
+    def sample_info(self):
+        """Host values of the last step_sampled / run_sampled with temperature > 0 (summed over a run's steps; synchronises): [lanes that
+        had a move, lanes whose played value is not their best value].  Raises before the first such call."""
+        h = (C.c_int64 * 2)()
+        _capi.check(self._lib.bgamd_env_sample_info(self._h, h), "sample_info")
+        return list(h)
+
     def step_search(self, top_k=8, roll=True, auto_reset=True, no_flip=False, want_index=False, only_player=None, slot=0, margin=None):
         """One 2-ply expectimax turn (include/bgamd.h, bgamd_env_step_search): the top_k best afterstates by the net (0 = all
         distinct ones) are re-scored by the average over the opponent's 21 rolls of the opponent's greedy reply, and the best of

@@ -61,6 +61,9 @@ SYMBOLS = [
     ("bgamd_env_step_greedy", C.c_int, [_P, C.c_int, C.c_float, C.c_int, _P]),
     ("bgamd_env_run_greedy", C.c_int, [_P, C.c_int, C.c_float, C.c_int, C.c_int64, _P]),
     ("bgamd_env_last_choice", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("bgamd_env_step_sampled", C.c_int, [_P, C.c_int, C.c_float, C.c_int, _P]),
+    ("bgamd_env_run_sampled", C.c_int, [_P, C.c_int, C.c_float, C.c_int, C.c_int64, _P]),
+    ("bgamd_env_sample_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("bgamd_env_step_search", C.c_int, [_P, C.c_int, C.c_int, _P]),
     ("bgamd_env_search_read", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("bgamd_env_step_search_filtered", C.c_int, [_P, C.c_int, C.c_int, C.c_float, _P]),

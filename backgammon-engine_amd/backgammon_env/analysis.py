@@ -63,7 +63,7 @@ def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, s
     return out
 
 
-def error_rate(player, judge, turns, top_k=4, epsilon=0.0, player_slot=0, judge_slot=0, on_turn=None):
+def error_rate(player, judge, turns, top_k=4, epsilon=0.0, player_slot=0, judge_slot=0, on_turn=None, temperature=None):
     """How much the player's moves lose by the judge's 2-ply search, over `turns` turns of every lane of `player`.
 
     player, judge: two VecGames with the same lane count; the player's weights in its slot player_slot play (one greedy step per turn
@@ -72,6 +72,8 @@ def error_rate(player, judge, turns, top_k=4, epsilon=0.0, player_slot=0, judge_
     reached (a game that ends stays on its final board for this, then restarts).  The judge is never stepped; the player plays on from
     wherever it stands and is left wherever the last turn took it.
     on_turn(turn, player, result): called after every turn's analysis with the analyze_moves result (device tensors).
+    temperature (None = greedy / epsilon): the player's moves are drawn with probability ~ exp(value / temperature) over its afterstates
+    (VecGame.step_sampled) instead; with epsilon > 0 as well: ValueError.
 
     -> dict: player1 / player2 / total, each a dict of
          decisions (moves analysed), unforced (of those: more than one afterstate), mistakes (error > 0), error_sum,
@@ -80,12 +82,17 @@ def error_rate(player, judge, turns, top_k=4, epsilon=0.0, player_slot=0, judge_
        and lane_turns = lanes x turns = decisions + passes + illegal + idle of total."""
     if player.n != judge.n:
         raise ValueError("error_rate needs two VecGames of equal lane count")
+    if temperature is not None and epsilon:
+        raise ValueError("epsilon and temperature are two ways to leave the greedy line: pass one of them")
     import torch
     counts = np.zeros((2, 6), np.int64)                    # per mover: decisions, unforced, mistakes, passes, illegal, idle
     sums = ([], [])
     for t in range(int(turns)):
         pre, mover = player.states(), player.turns()
-        player.step_greedy(roll=True, auto_reset=False, epsilon=epsilon, slot=player_slot)
+        if temperature is not None:
+            player.step_sampled(temperature, roll=True, auto_reset=False, slot=player_slot)
+        else:
+            player.step_greedy(roll=True, auto_reset=False, epsilon=epsilon, slot=player_slot)
         judge.set_states(pre, mover)
         judge.set_dice(player.dice())
         res = judge.analyze_moves(player.states(), top_k=top_k, slot=judge_slot)

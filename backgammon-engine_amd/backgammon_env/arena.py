@@ -9,7 +9,7 @@ import torch
 from . import F32, VecGame
 
 
-def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
+def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision, temperature=None):
     """policies: ("net", slot), ("search", slot, top_k) or ("random",).  The constructor seats the first mover by game parity
     (`Game(i % 2)`, train.py:265), no opening roll.
     -> (games finished, PLAYER1 wins, points int64 [7]: lanes by VecGame.outcomes() + 3, i.e. PLAYER2 backgammon, gammon, single game,
@@ -18,7 +18,9 @@ def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
     env.set_states(None, torch.arange(env.n, dtype=torch.int32) % 2)
     for t in range(max_turns):
         for player, pol in ((0, p1_policy), (1, p2_policy)):
-            if pol[0] == "net":
+            if pol[0] == "net" and temperature is not None:
+                env.step_sampled(temperature, auto_reset=False, only_player=player, slot=pol[1], precision=precision)
+            elif pol[0] == "net":
                 env.step_greedy(auto_reset=False, only_player=player, slot=pol[1], precision=precision)
             elif pol[0] == "search":
                 env.step_search(top_k=pol[2], auto_reset=False, only_player=player, slot=pol[1])
@@ -34,15 +36,22 @@ def _play(env: VecGame, p1_policy, p2_policy, max_turns: int, precision):
 
 
 def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000, precision=F32, plies_a: int = 1, plies_b: int = 1,
-                 top_k: int = 8):
+                 top_k: int = 8, epsilon: float = 0.0, temperature=None):
     """Win rate of A vs B (B = None: a uniformly random mover), sides alternated 50/50 as in
     evaluate_parallel (train.py:296-302): every lane plays one game with A as PLAYER1 and one with A as
     PLAYER2.  plies_a / plies_b = 2: that side moves by the 2-ply search (VecGame.step_search, top_k candidates, fp32 net).
+    temperature (None = greedy): a side that moves by its net (1 ply) draws every move with probability ~ exp(value / temperature) over
+    its afterstates (VecGame.step_sampled): varied games from one opening.  epsilon is accepted for symmetry with the self-play drivers
+    and must be 0 beside a temperature (ValueError); the arena does not explore uniformly.
     -> dict(games, a_wins, win_rate, a_as_p1, a_as_p2) and the match in points (a single game 1, a gammon 2, a backgammon 3;
     include/bgamd.h, bgamd_env_outcomes): a_points (A's points minus B's over both passes; a lane not finished at max_turns gives 0),
     ppg (a_points / games), a_gammons, a_backgammons, b_gammons, b_backgammons (games won by that much)."""
     if plies_a not in (1, 2) or plies_b not in (1, 2):
         raise ValueError("plies must be 1 or 2")
+    if temperature is not None and epsilon:
+        raise ValueError("epsilon and temperature are two ways to leave the greedy line: pass one of them")
+    if epsilon:
+        raise ValueError("the arena does not explore uniformly: epsilon must be 0")
     if plies_b == 2 and weights_b is None:
         raise ValueError("a random mover does not search")
     env.load_weights(weights_a, slot=0)
@@ -50,8 +59,8 @@ def head_to_head(env: VecGame, weights_a, weights_b=None, max_turns: int = 2000,
         env.load_weights(weights_b, slot=1)
     a = ("net", 0) if plies_a == 1 else ("search", 0, top_k)
     b = (("net", 1) if plies_b == 1 else ("search", 1, top_k)) if weights_b is not None else ("random",)
-    n1, w1, h1 = _play(env, a, b, max_turns, precision)      # A is PLAYER1
-    n2, w2, h2 = _play(env, b, a, max_turns, precision)      # A is PLAYER2
+    n1, w1, h1 = _play(env, a, b, max_turns, precision, temperature)      # A is PLAYER1
+    n2, w2, h2 = _play(env, b, a, max_turns, precision, temperature)      # A is PLAYER2
     a_wins = w1 + (n2 - w2)
     h = [x + y for x, y in zip(h1, reversed(h2))]            # from A's side: the second pass sign-flipped
     a_points = sum((k - 3) * c for k, c in enumerate(h))

@@ -622,14 +622,28 @@ class DeviceTDLambdaLearner:
         return float(sq.value), int(cnt.value)
 
 
-def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, episode=None, probe=None):
+def _run_policy(env, n_steps, auto_reset, epsilon, temperature, precision):
+    """n_steps self-play steps: greedy with uniform exploration (epsilon), or sampled at a temperature (VecGame.run_sampled) -- not both"""
+    if temperature is not None and epsilon:
+        raise ValueError("epsilon and temperature are two ways to leave the greedy line: pass one of them")
+    if temperature is not None:
+        env.run_sampled(n_steps, temperature, auto_reset=auto_reset, precision=precision)
+    else:
+        env.run_greedy(n_steps, auto_reset=auto_reset, epsilon=epsilon, precision=precision)
+
+
+def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, episode=None, probe=None, temperature=None):
     """One round of self-play from a frozen weight snapshot (train.py:527-547 semantics): every lane plays
     ONE game to the end, turns are logged. -> (rows [T, n, 8] int32, lengths [n], p1_won [n] bool).
     Round k of an env plays episode k of every lane (global game id lane_offset + lane + k * lane_stride): new dice,
     new opening roll and new exploration draws for every game, as play_game rolls fresh dice for every game
     (train.py:64-121).  episode=None continues the env's own round counter; an explicit value replays that round.
     probe: called once as probe(env) after the round's first 16 turns, while nearly every lane is still in its game (a read-only look
-    at a live step, e.g. env.choice_spread(): by the round's last step only the longest games are left)."""
+    at a live step, e.g. env.choice_spread(): by the round's last step only the longest games are left).
+    temperature (None = greedy / epsilon): every move is drawn with probability ~ exp(value / temperature) over the afterstates
+    (VecGame.step_sampled); with epsilon > 0 as well: ValueError."""
+    if temperature is not None and epsilon:
+        raise ValueError("epsilon and temperature are two ways to leave the greedy line: pass one of them")
     if episode is None:
         episode = getattr(env, "_round", 0)
     env._round = int(episode) + 1
@@ -638,7 +652,7 @@ def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, epi
     done_steps = 0
     while done_steps < max_plies:                      # 16 turns per call; finished games are frozen and skipped
         k = min(16, max_plies - done_steps)
-        env.run_greedy(k, auto_reset=False, epsilon=epsilon, precision=precision)
+        _run_policy(env, k, False, epsilon, temperature, precision)
         done_steps += k
         if probe is not None:
             probe(env)
@@ -678,10 +692,13 @@ class ContinuousSelfPlay:
         env.reset(episode=int(episode))
         self._collected = 0                        # env steps whose end records finished() has turned into games
 
-    def play(self, n_steps: int, epsilon: float = 0.0, precision=0):
+    def play(self, n_steps: int, epsilon: float = 0.0, precision=0, temperature=None):
+        """temperature (None = greedy / epsilon): sampled steps (VecGame.run_sampled); with epsilon > 0 as well: ValueError"""
+        if temperature is not None and epsilon:
+            raise ValueError("epsilon and temperature are two ways to leave the greedy line: pass one of them")
         if self.env.trajectory_step() + int(n_steps) - self._collected > self.R:
             raise ValueError("the window is longer than the ring: collect finished() first")
-        self.env.run_greedy(int(n_steps), auto_reset=True, epsilon=epsilon, precision=precision)
+        _run_policy(self.env, int(n_steps), True, epsilon, temperature, precision)
 
     def finished(self, keep_margin: int = 0):
         """The games that ended in the env steps played since the last call -> (game_lane, game_start, lengths, p1_won) device tensors,

@@ -186,7 +186,7 @@ __host__ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, u
     }
     return U4{c0, c1, c2, c3};
 }
-enum { STREAM_TURN = 0, STREAM_OPENING = 1 };
+enum { STREAM_TURN = 0, STREAM_OPENING = 1, STREAM_SAMPLE = 2 /* the sampled step's Gumbel noise, bg_sample.h */ };
 __host__ __device__ __forceinline__ int die_from_u32(uint32_t u) { return 1 + (int)(((uint64_t)u * 6u) >> 32); }
 
 // opening protocol of play_game, pysrc/TD(λ) model/train.py:89-97

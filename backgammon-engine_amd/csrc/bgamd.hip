@@ -878,6 +878,11 @@ struct bgamd_env {
     PrerollState pre;
     uint32_t *spread = nullptr;            // [5][n] per-lane words of bgamd_env_choice_spread (bg_health.h, SpreadView)
     bool greedy_stepped = false;           // a greedy step has been issued on this env: the arenas hold its rows
+    // the sampled step (bg_sample.h), allocated by the first one: smp_words = [2] counters | [n] per-lane maxima, smp_score [cap_rows]
+    unsigned long long *smp_words = nullptr;
+    float *smp_score = nullptr;
+    bool sampled = false;                  // a sampled step has been issued: bgamd_env_sample_info has something to read
+    hipStream_t smp_stream = nullptr;      // ... on this stream
 };
 
 namespace {
@@ -1130,7 +1135,7 @@ int bgamd_env_destroy(bgamd_env *env)
     const StagedView &sv = env->sv;
     free_all({v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq, v.chosen_val, v.rows, v.seqs,
               v.values, v.counters, env->a_ctr, sv.root_rows, sv.root_hidden, sv.d1, sv.d2, sv.f, sv.f2, sv.u_rows, sv.u_info, sv.best,
-              env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n, env->d_scalar, env->d_tmp, env->spread});
+              env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n, env->d_scalar, env->d_tmp, env->spread, env->smp_words, env->smp_score});
     for (hipEvent_t e : env->ev) hipEventDestroy(e);
     if (env->ev_fork) hipEventDestroy(env->ev_fork);
     if (env->ev_join) hipEventDestroy(env->ev_join);
@@ -1552,6 +1557,11 @@ static void launch_root_pass(bgamd_env *env, int slot, const uint4 *rows, long l
 
 }  // extern "C"
 
+// The sampled step's two passes (bg_sample.h) on s, between the value net and the apply: DEFINED at the end of this file, behind every other
+// kernel, for the reason given at launch_flt_select below.
+static void launch_sample_passes(bgamd_env *env, const EnvView &ev, const unsigned long long *tops, long long b_base, float temperature,
+                                 int n_cu, hipStream_t s);
+
 namespace {
 // The streams one greedy step is issued on: everything on `gen`, except the root pass of the incremental value net, which
 // goes to `root` (the env's side stream when it overlaps the doubles plies, else the same stream).
@@ -1568,6 +1578,7 @@ struct GreedyRun {
     bgamd_env *env;
     int flags, slot, precision, parity = 0;
     float epsilon;
+    float temperature = 0.0f;              // > 0: the sampled step (set after init() by bgamd_env_run_sampled, which passes epsilon 0)
     bool incremental;
     long long xall_nd = 1, xall_nl = 1;    // expand_all_kernel: workgroups for the doubles turns / for the non-doubles leaf stage
     StagedView sv;
@@ -1739,6 +1750,8 @@ struct GreedyRun {
             const int rc = launch_eval(env, slot, precision, &sv.tops[T_U], sv.cap_rows, sv.u_rows, env->v.values, sv.u_info, sv.best, se);
             if (rc) return rc;
         }
+        // sampled step: sv.best[g] becomes the pack of the row drawn with probability ~ exp(value / T) (never for a scoring pass)
+        if (temperature > 0.0f && !score_only) launch_sample_passes(env, ev, sv.tops, sv.b_base, temperature, ss.n_cu, s);
         ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
         if (epsilon > 0.0f) {                              // exploring lanes pick through their counted tasks (bounded work)
             KTimer t(env, s, 3);
@@ -1828,6 +1841,52 @@ int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision
 int bgamd_env_step_greedy(bgamd_env *env, int flags, float epsilon, int precision, void *stream)
 {
     return bgamd_env_run_greedy(env, flags, epsilon, precision, 1, stream);
+}
+
+int bgamd_env_run_sampled(bgamd_env *env, int flags, float temperature, int precision, int64_t n_steps, void *stream)
+{
+    if (!env || n_steps < 0 || !(temperature >= 0.0f) || __builtin_isinf(temperature)) return BGAMD_E_INVALID;      // (NaN fails the >=)
+    if (temperature == 0.0f) return bgamd_env_run_greedy(env, flags, 0.0f, precision, n_steps, stream);
+    HIPCHK(hipSetDevice(env->device));
+    GreedyRun run;
+    int rc = run.init(env, flags, 0.0f, precision);
+    if (rc) return rc;
+    run.temperature = temperature;
+    if (n_steps == 0) return BGAMD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!env->smp_words) {
+        HIPCHK(hipMalloc(&env->smp_words, (size_t)(env->v.n + 2) * 8));
+        HIPCHK(hipMalloc(&env->smp_score, (size_t)env->sv.cap_rows * 4));
+    }
+    HIPCHK(hipMemsetAsync(env->smp_words, 0, 2 * 8, s));            // the two counters: sums over the steps of this call
+    env->sampled = true;
+    env->smp_stream = s;
+    const StepStreams ss{s, (run.incremental && env->overlap) ? env->side : s, env->n_cu};
+    rc = run.begin(s);
+    if (rc) return rc;
+    for (int64_t step = 0; step < n_steps; ++step) {
+        rc = run.step(ss, step + 1 < n_steps);
+        if (rc) return rc;
+        env->greedy_stepped = true;
+    }
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_step_sampled(bgamd_env *env, int flags, float temperature, int precision, void *stream)
+{
+    return bgamd_env_run_sampled(env, flags, temperature, precision, 1, stream);
+}
+
+int bgamd_env_sample_info(bgamd_env *env, int64_t h_out[2])
+{
+    if (!env || !h_out || !env->sampled) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(h, env->smp_words, 2 * 8, hipMemcpyDeviceToHost, env->smp_stream));
+    HIPCHK(hipStreamSynchronize(env->smp_stream));
+    h_out[0] = (int64_t)h[0]; h_out[1] = (int64_t)h[1];
+    return BGAMD_OK;
 }
 
 // ---- what the 2-ply search, the pre-roll evaluation and the rollouts share --------------------------------------------------------
@@ -3458,4 +3517,26 @@ static void launch_flt_info(hipStream_t s, long long n, const SearchState &se)
 {
     hipLaunchKernelGGL(flt_info_kernel<1024>, dim3(1), dim3(1024), 0, s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff,
                        (const uint32_t *)se.c_key, se.min_searched, se.d_info);
+}
+
+// ---- the sampled step's passes (declared before GreedyRun; kernel templates first launched here, so that no other kernel moves) ------------
+namespace {
+#include "bg_sample.h"
+}
+
+static void launch_sample_passes(bgamd_env *env, const EnvView &ev, const unsigned long long *tops, long long b_base, float temperature,
+                                 int n_cu, hipStream_t s)
+{
+    const long long n = ev.n, cap_rows = env->sv.cap_rows;
+    const SampleView sm{env->smp_words + 2, env->smp_words, env->smp_score};
+    hipMemsetAsync(sm.pick, 0, (size_t)n * 8, s);
+    // a greedy step averages ~18 rows per game: no more workgroups than the rows can use.  Pass A is arithmetic (three Philox blocks and two
+    // logarithms per row) and takes every wave slot; pass B is a compare per row and ends in one atomic per workgroup and counter
+    const long long want = (n * 24 + SRCH_NT - 1) / SRCH_NT;
+    const long long ga = want < (long long)n_cu * 8 ? want : (long long)n_cu * 8, gb = want < (long long)n_cu * 2 ? want : (long long)n_cu * 2;
+    hipLaunchKernelGGL(sample_score_kernel<SRCH_NT>, dim3((unsigned)(ga < 1 ? 1 : ga)), dim3(SRCH_NT), 0, s, ev, tops, b_base, cap_rows,
+                       (const uint4 *)env->sv.u_rows, (const uint2 *)env->sv.u_info, (const float *)env->v.values,
+                       (const unsigned long long *)env->sv.best, temperature, sm);
+    hipLaunchKernelGGL(sample_pick_kernel<SRCH_NT>, dim3((unsigned)(gb < 1 ? 1 : gb)), dim3(SRCH_NT), 0, s, n, tops, b_base, cap_rows,
+                       (const uint2 *)env->sv.u_info, (const float *)env->v.values, env->sv.best, sm);
 }

@@ -4,7 +4,7 @@ the judge's net over the player's top --top-k moves and the one it played (analy
 a move is what the judge's best move is worth at 2 plies minus what the played one is, in win probability.  Every unforced turn
 counts -- not one bit per game, as in an arena.  One run is one run: the figures move with the seed.
 
-    python examples/error_rate.py --player CKPT --judge CKPT --games 4096 --turns 64 --top-k 4 [--epsilon 0.1]
+    python examples/error_rate.py --player CKPT --judge CKPT --games 4096 --turns 64 --top-k 4 [--epsilon 0.1 | --temperature 0.05]
 
 CKPT: a file of 25 601 float32 (W1 | b1 | W2 | b2); left out: the bundled checkpoint.
 """
@@ -40,14 +40,17 @@ def main():
     ap.add_argument("--turns", type=int, default=64, help="turns played and judged per lane")
     ap.add_argument("--top-k", type=int, default=4, help="the judge searches the player's K best moves by 1-ply value and the played one (0 = all)")
     ap.add_argument("--epsilon", type=float, default=0.0, help="the player explores: a random move with this probability")
+    ap.add_argument("--temperature", type=float, default=None,
+                    help="the player draws every move with probability ~ exp(value / T) over its afterstates (not beside --epsilon)")
     ap.add_argument("--seed", type=int, default=1)
     a = ap.parse_args()
     player, judge = bg.VecGame(a.games, seed=a.seed), bg.VecGame(a.games, seed=a.seed)
     player.load_weights(table(a.player))
     judge.load_weights(table(a.judge))
-    r = analysis.error_rate(player, judge, a.turns, top_k=a.top_k, epsilon=a.epsilon)
+    r = analysis.error_rate(player, judge, a.turns, top_k=a.top_k, epsilon=a.epsilon, temperature=a.temperature)
     print("player %s  judge %s (2-ply, top_k %d)  games %d  turns %d  epsilon %g  seed %d" %
-          (os.path.basename(a.player or "bundled"), os.path.basename(a.judge or "bundled"), a.top_k, a.games, a.turns, a.epsilon, a.seed))
+          (os.path.basename(a.player or "bundled"), os.path.basename(a.judge or "bundled"), a.top_k, a.games, a.turns, a.epsilon, a.seed) +
+          ("" if a.temperature is None else "  temperature %g" % a.temperature))
     cols = ("decisions", "unforced", "mistakes", "error_sum", "error_rate", "agreement", "passes", "illegal")
     print("%-8s" % "" + "".join("%14s" % c for c in cols))
     for side in ("player1", "player2", "total"):

@@ -109,7 +109,7 @@ def run_continuous(a, env, arena, L, group, world, prec, say, guard, n_classic=0
     for b in range(a.burn_in_windows):                 # lanes out of step before the first window that counts (weights: the initial ones)
         if b == 0:
             guard.load(env, "burn-in")
-        sp.play(a.window_steps, epsilon=a.eps if a.eps is not None else a.eps_start, precision=prec)
+        sp.play(a.window_steps, epsilon=a.eps if a.eps is not None else a.eps_start, precision=prec, temperature=a.temperature)
         sp.finished()
     held, held_all = None, 0                           # finished games held back until --min-window-games (per rank, summed over the ranks) have accumulated
     pending, th = None, None
@@ -127,7 +127,7 @@ def run_continuous(a, env, arena, L, group, world, prec, say, guard, n_classic=0
             th.start()
         table, h_rows, spread = None, None, None
         if r < n_win:
-            sp.play(a.window_steps, epsilon=eps, precision=prec)
+            sp.play(a.window_steps, epsilon=eps, precision=prec, temperature=a.temperature)
             spread = env.choice_spread()               # the window's last self-play step
             if a.health_rows > 0:                      # rows of this window out of the ring, spread over at least 16 of its steps
                 s1 = env.trajectory_step()
@@ -193,6 +193,9 @@ def main():
     ap.add_argument("--eps-start", type=float, default=0.1, help="exploration rate of the first round (train.py:446)")
     ap.add_argument("--eps-end", type=float, default=0.0, help="... decaying linearly to this over the run (train.py:531)")
     ap.add_argument("--eps", type=float, default=None, help="fixed exploration rate (overrides the linear decay)")
+    ap.add_argument("--temperature", type=float, default=None,
+                    help="self-play draws every move with probability ~ exp(value / T) over the afterstates (VecGame.step_sampled) instead of "
+                         "exploring uniformly: the exploration rate is then 0 (an --eps > 0 beside it is refused)")
     ap.add_argument("--sub-round", type=int, default=0, help="replay the round in sub-rounds of this many games, weights "
                     "refreshed between them (0 = the whole round lock-step)")
     ap.add_argument("--slots", type=int, default=0, help="streamed replay: this many slots replay the round's games one after another "
@@ -248,6 +251,10 @@ def main():
                          "step); bf16 = config 5's speed mode (single bf16 weights on the MFMA pipe, outside the 1e-5 bound; the learner keeps "
                          "fp32 traces and weights); auto = f16x2 below 16 384 games per rank")
     a = ap.parse_args()
+    if a.temperature is not None:
+        if a.eps:
+            raise ValueError("--eps and --temperature are two ways to leave the greedy line: pass one of them")
+        a.eps = 0.0
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     group = None
     if world > 1:
@@ -290,7 +297,7 @@ def main():
         eps = a.eps if a.eps is not None else a.eps_start + (a.eps_end - a.eps_start) * (games_done / total_games)
         guard.load(env, f"round {r + 1} ({games_done} games, {turns} turns replayed)")
         early = {}
-        rows, lengths, p1_won = play_round(env, max_plies=a.max_plies, epsilon=eps, precision=prec,     # round r = episode r: fresh dice
+        rows, lengths, p1_won = play_round(env, max_plies=a.max_plies, epsilon=eps, precision=prec, temperature=a.temperature,     # round r = episode r: fresh dice
                                            probe=lambda e: early.update(e.choice_spread()))
         spread = env.choice_spread()                         # the round's last self-play step
         if r < 2:                                            # every round must play NEW games

@@ -188,6 +188,38 @@ int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision
 int bgamd_env_last_choice(bgamd_env *env, int32_t *d_chosen, int32_t *d_count, int8_t *d_seq /*[n,4,2]*/,
                           int32_t *d_seq_len, float *d_value, void *stream);
 
+/* ---- the temperature-sampled step: a move drawn with probability ~ exp(value / T) over the afterstates the net has scored ---------------
+ * A greedy step in which a lane with a move, mover m, plays a SAMPLED afterstate instead of its best one.  The rule, for temperature T > 0:
+ *   - candidates: the rows the value net evaluated for the lane (what bgamd_env_unique_rows_info / _read list).  Two rows that hold the
+ *     same afterstate under two keys (about 3 % of the rows) count as ONE candidate;
+ *   - mover-side value: a_i = v_i for PLAYER1, -v_i for PLAYER2, of the stored fp32 value v_i; a_best the same of the lane's best row (the
+ *     greedy step's choice); d_i = a_i - a_best <= 0, one fp32 subtraction;
+ *   - the draw is Gumbel-max: row i gets u_i in (0, 1) and the score  s_i = d_i / T + g_i,  g_i = -log(-log(u_i)),  formed in fp32 as
+ *     q = d_i / T (IEEE division), L1 = logf(u_i), L2 = logf(-L1), s_i = q - L2.  The lane plays the row with the largest score; on
+ *     bit-equal scores the smallest key (the earliest reference-order index), the greedy step's tie rule.  Because d / T is used and not
+ *     a / T, every finite T > 0 is safe: the best row scores 0 + g, the others go to -inf at worst, no NaN arises.  As T -> 0 the step
+ *     becomes the greedy step (up to the choice among rows whose values are bit-equal to the best);
+ *   - u_i is a counter-based function of (env seed, game id, ply, the row's eight 32-bit plane words with the turn bit cleared) and of
+ *     nothing else -- not of the key, the row's place, the lane count or the launch.  With P = Philox4x32-10 and key = (seed_lo, seed_hi)
+ *     unless stated:  A = P(counter = row[0..3]);  B = P(counter = row[4..7] ^ A);  C = P(counter = (gid_lo, gid_hi, ply, 2), key = (B.x,
+ *     B.y)) -- 2 is the SAMPLE stream, beside TURN = 0 and OPENING = 1 --;  u = (2 (C.x >> 9) + 1) 2^-24.  (23 random bits and a half, so
+ *     that every u is an fp32 number: 2^-24 <= u <= 1 - 2^-24.)  Rows holding the same afterstate therefore draw the same u, score
+ *     bit-equal and fall to the tie rule: the distribution is exactly softmax(a / T) over the DISTINCT afterstates;
+ *   - T = 0 is the greedy step itself: the same launches, bit-identical results.  T < 0, NaN or +inf: BGAMD_E_INVALID.  There is no
+ *     epsilon: the sampled entry points do not explore uniformly;
+ *   - everything else is the greedy step: a lane without a move, a lane that does not take part and a finished lane keep what they keep
+ *     there; bgamd_env_last_choice reports the SAMPLED row's sequence and value; every flag, both weight slots, every precision, the
+ *     trajectory log and ring and bgamd_env_stats work unchanged.
+ * Two small passes over the evaluated rows run between the value net and the apply (csrc/bg_sample.h); their scratch is allocated by the
+ * first sampled step.  The 2-ply search, the rollouts and the analysis never sample. */
+int bgamd_env_step_sampled(bgamd_env *env, int flags, float temperature, int precision, void *stream);
+/* n_steps sampled steps back to back, as bgamd_env_run_greedy: the same games as n_steps calls of bgamd_env_step_sampled */
+int bgamd_env_run_sampled(bgamd_env *env, int flags, float temperature, int precision, int64_t n_steps, void *stream);
+/* Host values of the last call of either with T > 0 (summed over a run's steps; SYNCHRONISES that call's stream): h_out[0] lanes that had
+ * a move, h_out[1] of those the lanes that left the arg-max: the value of the row they played is not bit-equal to their best value.
+ * BGAMD_E_INVALID before the first such call. */
+int bgamd_env_sample_info(bgamd_env *env, int64_t h_out[2]);
+
 /* ---- 2-ply expectimax move search (TD-Gammon's 2-ply) -------------------------------------------------------------------------
  * One searched turn for every live lane that takes part (flags: BGAMD_ROLL, BGAMD_AUTO_RESET, BGAMD_NO_FLIP, BGAMD_WANT_INDEX,
  * BGAMD_ONLY_P1/P2 and BGAMD_WEIGHTS_SLOT1 mean what they mean for the greedy step; no epsilon; the F32 incremental value net only):
