@@ -537,6 +537,27 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_set_trajectory_ring(self._h, _ptr(rows), int(ring_steps), _ptr(end)), "set_trajectory_ring")
         return rows, end
 
+    def record_search_log(self, max_plies: int | None):
+        """Log of the search steps' turns (bgamd_env_set_search_log): while set, every step_search writes, for each lane that takes part,
+        at [ply, lane]: the pre-move row, the played afterstate with the opponent to roll, V2 of the played candidate (NaN where the lane
+        was not searched: a filtered step's singleton, a lane without a move) and its 1-ply value -> (rows int32 [T, n, 8], after int32
+        [T, n, 8], target float32 [T, n], v1 float32 [T, n]); the rows start as zeros, target and v1 as NaN.  While it is set, search steps
+        with auto_reset and every other kind of step raise.  None drops it."""
+        if max_plies is None:
+            self._slog = None
+            _capi.check(self._lib.bgamd_env_set_search_log(self._h, None, None, None, None, 0), "set_search_log")
+            return None
+        T = int(max_plies)
+        if T <= 0:                                             # BGAMD_E_INVALID, as the library answers it; nothing is allocated for it
+            _capi.check(-1, "set_search_log")
+        rows = torch.zeros((T, self.n, 8), dtype=torch.int32, device=self.device)
+        after = torch.zeros((T, self.n, 8), dtype=torch.int32, device=self.device)
+        target = torch.full((T, self.n), float("nan"), dtype=torch.float32, device=self.device)
+        v1 = torch.full((T, self.n), float("nan"), dtype=torch.float32, device=self.device)
+        _capi.check(self._lib.bgamd_env_set_search_log(self._h, _ptr(rows), _ptr(after), _ptr(target), _ptr(v1), T), "set_search_log")
+        self._slog = (rows, after, target, v1)
+        return self._slog
+
     def trajectory_step(self) -> int:
         """env steps logged into the ring so far (a host counter: no synchronisation)"""
         return int(self._lib.bgamd_env_trajectory_step(self._h))

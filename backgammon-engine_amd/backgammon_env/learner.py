@@ -406,24 +406,52 @@ class DeviceTDLambdaLearner:
         -> the mean squared error of every epoch, [Σ δ² / rows that counted], as the steps saw it (fit_stats)."""
         rows = self._pack_rows(states28, turn).reshape(-1, 8)
         y = torch.as_tensor(targets, dtype=torch.float32).to(rows.device).reshape(-1)
+        if int(y.numel()) != int(rows.shape[0]):
+            raise ValueError("one target per position")
+        return self.fit_rows(rows, y, epochs=epochs, batch=batch, seed=seed, alpha=alpha, batch_scale=batch_scale)
+
+    def fit_rows(self, rows, targets, epochs: int = 1, batch: int = 4096, seed: int = 0, alpha=None, batch_scale=None):
+        """fit on rows that are packed already: rows int32 [n, 8] 32-byte rows (pack_rows, a trajectory or search log; the turn bit is the
+        side to move), targets [n].  The same epochs, batches, steps and return value as fit, which packs and calls this.  The per-epoch
+        errors are read with fit_stats, which clears the counters as it reads: what those reads gave, summed over the epochs, stays in
+        last_fit_stats = (Σ δ², rows that counted, rows skipped)."""
+        rows = torch.as_tensor(rows, device=self.device).to(torch.int32).reshape(-1, 8)
+        y = torch.as_tensor(targets, dtype=torch.float32).to(rows.device).reshape(-1)
         n = int(rows.shape[0])
         if int(y.numel()) != n:
-            raise ValueError("one target per position")
+            raise ValueError("one target per row")
         if batch_scale is None:
             batch_scale = 24.0 / int(batch)
         self.fit_stats()
-        mse, epoch = [], 0
+        mse, epoch, total = [], 0, [0.0, 0, 0]
+
+        def close_epoch():
+            sq, cnt, skipped = self.fit_stats()
+            mse.append(sq / max(cnt, 1))
+            total[0] += sq; total[1] += cnt; total[2] += skipped
         for e, idx in fit_batches(n, epochs, batch, seed):
             if e != epoch:
-                sq, cnt, _ = self.fit_stats()
-                mse.append(sq / max(cnt, 1))
+                close_epoch()
                 epoch = e
             idx = idx.to(rows.device)
             self.fit_step(rows[idx], y[idx], alpha=alpha, batch_scale=batch_scale)
         if n and epochs > 0:
-            sq, cnt, _ = self.fit_stats()
-            mse.append(sq / max(cnt, 1))
+            close_epoch()
+        self.last_fit_stats = tuple(total)
         return mse
+
+    def fit_search(self, after, target, lengths, epochs: int = 1, batch: int = 4096, seed: int = 0, alpha=None, batch_scale=None):
+        """Fits the net to its own 2-ply search: after int32 [T, n, 8] and target float32 [T, n] of a search log (play_round_search,
+        VecGame.record_search_log), lengths [n] the logged turns per lane (0 = leave the lane out).  The entries with ply < lengths[lane]
+        are flattened, ply-major, and handed to fit_rows.  An entry whose target is NaN -- a turn that was not searched -- stays in: the
+        fit step skips and counts it (fit_stats).  -> fit_rows' per-epoch mean squared error."""
+        after = torch.as_tensor(after, device=self.device).to(torch.int32)
+        T, n = int(after.shape[0]), int(after.shape[1])
+        y = torch.as_tensor(target, device=self.device).to(torch.float32).reshape(T, n)
+        ln = torch.as_tensor(lengths, device=self.device).to(torch.int64).reshape(1, n)
+        valid = torch.arange(T, device=self.device, dtype=torch.int64).reshape(T, 1) < ln
+        return self.fit_rows(after.reshape(T, n, 8)[valid], y[valid], epochs=epochs, batch=batch, seed=seed, alpha=alpha,
+                             batch_scale=batch_scale)
 
     def replay_rows(self, rows, lengths, p1_won, group=None, batch_scale: float = 1.0, split_apply: bool = False,
                     sub_round: int = 0, slots: int = 0):
@@ -668,6 +696,34 @@ def play_round(env, max_plies: int = 512, epsilon: float = 0.0, precision=0, epi
     T = int(lengths.max().item()) if lengths.numel() else 0
     env.record_trajectory(None)
     return traj[:max(T, 1)], lengths, p1_won
+
+
+def play_round_search(env, max_plies: int = 512, top_k: int = 5, margin=None, episode=None, slot: int = 0):
+    """play_round with every turn chosen by the 2-ply search step (VecGame.step_search: the top_k best afterstates by the net, margin None
+    = all of them searched, else the filtered step) and logged by the search log (VecGame.record_search_log): every lane plays ONE game
+    to the end from the frozen weights of `slot`, no auto-reset; the same episode / round bookkeeping as play_round.
+    -> (rows [T, n, 8], lengths [n], p1_won [n], after [T, n, 8], target [T, n], v1 [T, n]): the first three are what play_round
+    returns (DeviceTDLambdaLearner.replay_rows takes them unchanged; unfinished games have length 0), the others the played
+    afterstates with the opponent to roll, their 2-ply values (NaN where the turn was not searched) and their 1-ply values
+    (DeviceTDLambdaLearner.fit_search takes after, target and lengths)."""
+    if episode is None:
+        episode = getattr(env, "_round", 0)
+    env._round = int(episode) + 1
+    rows, after, target, v1 = env.record_search_log(max_plies)
+    env.reset(episode=int(episode))
+    for step in range(int(max_plies)):                 # finished games are frozen and skipped; a look at the flags every 16 turns
+        env.step_search(top_k=top_k, auto_reset=False, slot=slot, margin=margin)
+        if step % 16 == 15 and bool(((env.flags() & 4) != 0).all()):
+            break
+    flags = env.flags()
+    done = (flags & 4) != 0
+    ply, _ = env.progress()
+    lengths = torch.where(done, ply + 1, torch.zeros_like(ply))        # unfinished games are not replayed
+    lengths = torch.clamp(lengths, max=max_plies)
+    p1_won = ((flags >> 1) & 1) == 0
+    T = max(int(lengths.max().item()) if lengths.numel() else 0, 1)
+    env.record_search_log(None)
+    return rows[:T], lengths, p1_won, after[:T], target[:T], v1[:T]
 
 
 class ContinuousSelfPlay:

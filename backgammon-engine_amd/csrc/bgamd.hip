@@ -755,6 +755,13 @@ struct SearchState {
     void release() { free_all({cnt, off, fill, kept, koff, max, grp, rank, c_rows, c_key, c_v1, c_v2, c_rval, skept, soff, vmap, d_info}); *this = SearchState{}; }
 };
 
+// search log (bgamd_env_set_search_log, bg_search_log.h): the caller's buffers, [plies][n] each; rows NULL = no log
+struct SearchLog {
+    uint4 *rows = nullptr, *after = nullptr;
+    float *target = nullptr, *v1 = nullptr;
+    long long plies = 0;
+};
+
 // move analysis (bgamd_env_analyze_moves, bg_analysis.h): the per-lane results of the last one and its summary
 struct AnalysisState {
     AnaView v{};
@@ -871,6 +878,7 @@ struct bgamd_env {
     // whole number of 16-byte units, so that the rollout's one fill launch clears both.  48 bytes, allocated with every env (env_allocate).
     unsigned long long *a_ctr = nullptr;
     SearchState srch;
+    SearchLog slog;                        // set: search steps log into it, every other step is refused (bgamd_env_set_search_log)
     int ro_plies = 1, ro_top_k = 0;        // bgamd_env_rollout_policy: who plays the trials' turns (1 = the greedy step)
     float ro_margin = 0.0f;
     AnalysisState ana;
@@ -1411,6 +1419,7 @@ int bgamd_env_candidates_read(bgamd_env *env, int64_t first, int64_t n_rows, int
 int bgamd_env_step_random(bgamd_env *env, int flags, const uint32_t *d_choice_u32, void *stream)
 {
     ENV_GUARD(env);
+    if (env->slog.rows) return BGAMD_E_INVALID;                      // a search log is set: no step but the search's (no hole in a log)
     hipStream_t s = (hipStream_t)stream;
     const long long n = env->v.n;
     HIPCHK(hipMemsetAsync(env->rv.top, 0, 8, s));
@@ -1431,6 +1440,7 @@ int bgamd_env_step_random(bgamd_env *env, int flags, const uint32_t *d_choice_u3
 int bgamd_env_step_random_walk(bgamd_env *env, int flags, const uint32_t *d_choice_u32, void *stream)
 {
     ENV_GUARD(env);
+    if (env->slog.rows) return BGAMD_E_INVALID;                      // (as bgamd_env_step_random)
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(step_random_kernel, grid1(env->v.n, 64), dim3(64), 0, s, env->v, flags, d_choice_u32);
     HIPCHK(hipGetLastError());
@@ -1820,6 +1830,7 @@ extern "C" {
 int bgamd_env_run_greedy(bgamd_env *env, int flags, float epsilon, int precision, int64_t n_steps, void *stream)
 {
     if (!env || n_steps < 0) return BGAMD_E_INVALID;
+    if (env->slog.rows) return BGAMD_E_INVALID;                      // a search log is set: no step but the search's (no hole in a log)
     HIPCHK(hipSetDevice(env->device));
     GreedyRun run;
     int rc = run.init(env, flags, epsilon, precision);
@@ -1846,6 +1857,7 @@ int bgamd_env_step_greedy(bgamd_env *env, int flags, float epsilon, int precisio
 int bgamd_env_run_sampled(bgamd_env *env, int flags, float temperature, int precision, int64_t n_steps, void *stream)
 {
     if (!env || n_steps < 0 || !(temperature >= 0.0f) || __builtin_isinf(temperature)) return BGAMD_E_INVALID;      // (NaN fails the >=)
+    if (env->slog.rows) return BGAMD_E_INVALID;                      // (as bgamd_env_run_greedy)
     if (temperature == 0.0f) return bgamd_env_run_greedy(env, flags, 0.0f, precision, n_steps, stream);
     HIPCHK(hipSetDevice(env->device));
     GreedyRun run;
@@ -1941,6 +1953,8 @@ static void launch_flt_fanout(hipStream_t s, const EnvView &lanes, long long v0,
 static void launch_flt_reduce(hipStream_t s, long long n, const SearchState &se, unsigned long long *best, unsigned long long *err,
                               unsigned long long *scratch_err);
 static void launch_flt_info(hipStream_t s, long long n, const SearchState &se);
+// the search log's pass (bg_search_log.h): declared here and defined at the very end of the file for the same reason
+static void launch_search_log(hipStream_t s, const bgamd_env *env, int flags, uint32_t min_searched);
 
 // d_played NULL: the search step.  Else the analysis of the played afterstates d_played [n][28]: the same stages with the played row
 // matched and forced into the kept set, and in place of the choice and the apply launch the per-lane results and their summary.
@@ -1949,6 +1963,10 @@ static void launch_flt_info(hipStream_t s, long long n, const SearchState &se);
 static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, const float *margin, hipStream_t s)
 {
     if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
+    // ... into those two.  Its own log (bgamd_env_set_search_log) is written by the search step alone; the analysis applies nothing and
+    // ignores it.  With auto-reset a lane's next game would write over its last one.
+    const bool logged = env->slog.rows && !d_played;
+    if (logged && (flags & BGAMD_AUTO_RESET)) return BGAMD_E_INVALID;
     if (!env->net.has_weights[(flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0]) return BGAMD_E_NOWEIGHTS;
     const long long n = env->v.n;
     SearchState &se = env->srch;
@@ -2062,6 +2080,7 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
         hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
                            (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
                            (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err);
+    if (logged) launch_search_log(s, env, flags, margin ? 2u : 1u);
     const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
     hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
     HIPCHK(hipGetLastError());
@@ -2608,6 +2627,15 @@ int bgamd_env_set_trajectory_ring(bgamd_env *env, void *d_rows, int64_t ring_ste
 }
 
 int64_t bgamd_env_trajectory_step(const bgamd_env *env) { return env ? env->traj_step : 0; }
+
+int bgamd_env_set_search_log(bgamd_env *env, void *d_rows, void *d_after, float *d_target, float *d_v1, int64_t max_plies)
+{
+    if (!env || (d_rows && max_plies <= 0)) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    env->slog = SearchLog{};
+    if (d_rows) env->slog = SearchLog{(uint4 *)d_rows, (uint4 *)d_after, d_target, d_v1, (long long)max_plies};
+    return BGAMD_OK;
+}
 
 int bgamd_env_get_progress(bgamd_env *env, int32_t *d_ply, int32_t *d_episode, void *stream)
 {
@@ -3539,4 +3567,17 @@ static void launch_sample_passes(bgamd_env *env, const EnvView &ev, const unsign
                        (const unsigned long long *)env->sv.best, temperature, sm);
     hipLaunchKernelGGL(sample_pick_kernel<SRCH_NT>, dim3((unsigned)(gb < 1 ? 1 : gb)), dim3(SRCH_NT), 0, s, n, tops, b_base, cap_rows,
                        (const uint2 *)env->sv.u_info, (const float *)env->v.values, env->sv.best, sm);
+}
+
+// ---- the search log's pass (declared before search_stages; a kernel template first launched here, so that no other kernel moves) ---------
+namespace {
+#include "bg_search_log.h"
+}
+
+static void launch_search_log(hipStream_t s, const bgamd_env *env, int flags, uint32_t min_searched)
+{
+    const SearchState &se = env->srch;
+    hipLaunchKernelGGL(srch_log_kernel<SRCH_NT>, grid1(env->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, flags, (const uint4 *)env->sv.root_rows,
+                       (const unsigned long long *)env->sv.best, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows,
+                       (const uint32_t *)se.c_key, (const float *)se.c_v1, (const float *)se.c_v2, min_searched, env->slog);
 }

@@ -276,6 +276,33 @@ int bgamd_env_step_search_filtered(bgamd_env *env, int flags, int top_k, float m
  * values without a launch): a search step launches nothing for them. */
 int bgamd_env_search_info(bgamd_env *env, int64_t h_out[4]);
 
+/* ---- search log: the search steps' turns for the learner (TD replay of searched games, fitting the net to its own search) ------------
+ * d_rows and d_after are [max_plies][n] x 32 B rows (16-byte aligned) in the trajectory log's format (8 planes, turn in plane 0 bit 31);
+ * d_target and d_v1 are [max_plies][n] floats.  d_rows == NULL disables the log; with d_rows set any of the other three may be NULL (that
+ * part is not written); max_plies <= 0 with d_rows set: BGAMD_E_INVALID.  The setting sticks to the env and is separate from
+ * bgamd_env_set_trajectory and the ring log: a search step still refuses to run while either of those is set.
+ * While the log is set, every bgamd_env_step_search and bgamd_env_step_search_filtered writes one entry for each lane that is live and
+ * takes part (not finished or frozen, not left out by BGAMD_ONLY_P1/P2), at index ply * n + lane, ply = the lane's ply when the step
+ * begins -- the trajectory log's rule.  Plies >= max_plies are dropped: nothing is written past the buffers.  The entry:
+ *   rows    the pre-move row: the lane's board and the mover's turn bit, bit-identical to what a greedy step would put into the
+ *           trajectory log for that turn;
+ *   after   the afterstate that is played, with the turn bit of the side that is NOT the mover -- a terminal afterstate too, and with
+ *           BGAMD_NO_FLIP too.  A lane without a move logs its own board with that bit;
+ *   target  V2 of the played candidate, bit-equal to the value bgamd_env_last_choice reports and to bgamd_env_search_read's v2 of it,
+ *           for every lane whose candidates were searched: after bgamd_env_step_search every lane with a move, after the filtered step
+ *           every lane that kept >= 2 candidates (a terminal candidate's V2 is its exact outcome).  A lane that was not searched -- the
+ *           filtered step's singleton, a lane without a move -- gets a quiet NaN: bgamd_td_fit_step skips and counts such a row, so no
+ *           mask is needed downstream.  For a non-terminal played candidate the target is a function of the logged `after` row and the
+ *           weights alone: V2 is the 1-ply pre-roll lookahead of that position (bgamd_env_evaluate_preroll's roll values, item 4's sum);
+ *   v1      the 1-ply value of the played candidate (a terminal candidate: its exact outcome); a lane without a move: a quiet NaN.
+ * Lanes that take no part write nothing: their slots keep what the caller put there.  One pass of a thread per lane between the V2
+ * reduction and the apply (csrc/bg_search_log.h), launched only while the log is set.
+ * Refusals while the log is set (BGAMD_E_INVALID): a search step with BGAMD_AUTO_RESET (a lane's next game would write over its last
+ * one); bgamd_env_step_greedy / run_greedy / step_sampled / run_sampled / step_random / step_random_walk (a turn played by them would be
+ * a hole in the log).  bgamd_env_analyze_moves, bgamd_env_rollout and bgamd_env_evaluate_preroll ignore the log: they apply nothing to
+ * the env, and the rollout's trial env never has one. */
+int bgamd_env_set_search_log(bgamd_env *env, void *d_rows, void *d_after, float *d_target, float *d_v1, int64_t max_plies);
+
 /* ---- move analysis: a played move scored against the 2-ply search (GNU Backgammon's "analyse game") ----------------------------------
  * Every lane's decision is its current board, side to move and dice as they stand (bgamd_env_set_states / bgamd_env_set_dice);
  * d_played28[g] is the afterstate that was played from lane g (reference layout; the mover's turn bit is implied).  flags: only

@@ -4,7 +4,10 @@ after a warm-up (HIP events around `--steps` back-to-back steps).  One JSON line
 
 --margin M[,M...]: after each unfiltered configuration, the filtered step (bgamd_env_step_search_filtered) with each margin from the same
 starting positions: ms per step, the virtual roots scored, the lanes searched and the kept candidates of the last step
-(bgamd_env_search_info), and the share of lanes whose choice differs from the unfiltered step's on one common set of positions and dice."""
+(bgamd_env_search_info), and the share of lanes whose choice differs from the unfiltered step's on one common set of positions and dice.
+
+--log: what the search log's pass (bgamd_env_set_search_log, csrc/bg_search_log.h) costs a step -- the filtered step at 65 536 lanes,
+top_k 5, margin 0.04, without auto-reset, from the same positions with and without the log set, alternating; one JSON line."""
 import argparse
 import json
 import os
@@ -36,6 +39,41 @@ def _time(fn, steps, warmup, regions):
     return statistics.median(ms), ms
 
 
+def log_cost(a):
+    """the filtered step with and without the search log, alternating: every region starts from the same positions (10 greedy steps past
+    the opening; the log is set after them -- a greedy step is refused while it is set) and times `steps` back-to-back search steps"""
+    import backgammon_env as bg
+    n, top_k, margin, steps = 65536, 5, 0.04, a.steps
+    w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
+    env = bg.VecGame(n, seed=1)
+    env.load_weights(w)
+    ms = {False: [], True: []}
+    for region in range(-a.warmup, a.regions):
+        for logged in ((False, True) if region % 2 == 0 else (True, False)):
+            env.reset()
+            env.run_greedy(10, auto_reset=False)
+            if logged:
+                env.record_search_log(10 + steps)
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(steps):
+                env.step_search(top_k=top_k, auto_reset=False, margin=margin)
+            t1.record()
+            t1.synchronize()
+            if logged:
+                env.record_search_log(None)
+            if region >= 0:
+                ms[logged].append(t0.elapsed_time(t1) / steps)
+    env.close()
+    plain, logd = statistics.median(ms[False]), statistics.median(ms[True])
+    print(json.dumps({"search_log_cost": {"n": n, "top_k": top_k, "margin": margin, "steps_per_region": steps, "regions": a.regions,
+                                          "ms_per_step_without_log": round(plain, 4), "ms_per_step_with_log": round(logd, 4),
+                                          "difference_ms": round(logd - plain, 4), "bytes_per_lane_and_step": 72,
+                                          "regions_ms_without": [round(x, 4) for x in ms[False]],
+                                          "regions_ms_with": [round(x, 4) for x in ms[True]]}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="4096,16384,65536")
@@ -44,7 +82,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--regions", type=int, default=5)
     ap.add_argument("--margin", default="", help="comma-separated margins of the filtered step (none: the unfiltered step only)")
+    ap.add_argument("--log", action="store_true", help="the cost of the search log's pass instead (see above)")
     a = ap.parse_args()
+    if a.log:
+        return log_cost(a)
     import backgammon_env as bg
     w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
     out = []
