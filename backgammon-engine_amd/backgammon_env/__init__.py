@@ -376,7 +376,8 @@ class VecGame:
         return f, m
 
     def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
-                per_trial=False, variance_reduction=False, outcomes=False, plies=1, top_k=4, margin=float("inf")):
+                per_trial=False, variance_reduction=False, outcomes=False, plies=1, top_k=4, margin=float("inf"), groups=None,
+                group_offset=0):
         """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
         move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
         trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
@@ -390,27 +391,49 @@ class VecGame:
         (float64, PLAYER1's cubeless equity in points; a truncated trial counts 2 x - 1 of its net value x), with per_trial trial_points
         [P, T] (int8, 0 = truncated).  The other outputs are the same as without it.
         plies = 2: every turn of every trial is chosen by the filtered 2-ply search with (top_k, margin) instead of the greedy step
-        (bgamd_env_rollout_policy, set for this call; 1 is put back afterwards).  Same trials, same dice."""
+        (bgamd_env_rollout_policy, set for this call; 1 is put back afterwards).  Same trials, same dice.
+        groups (int sequence or tensor [P]): dice groups (bgamd_env_rollout_grouped) -- trial i of position p rolls the dice of game id
+        (group_offset + groups[p]) * trials + i instead, so the positions of a group share their trials' dice; every output stays indexed
+        by position, and position p's are those of the single-position call with position_offset = group_offset + groups[p].
+        rollout_paired() then reads the differences inside a group.  groups with a non-zero position_offset: ValueError."""
+        if groups is not None and int(position_offset) != 0:
+            raise ValueError("rollout: groups set the dice ids; pass group_offset, not position_offset")
+        if groups is None and int(group_offset) != 0:
+            raise ValueError("rollout: group_offset goes with groups; without them pass position_offset")
         if int(plies) != 1:
             _capi.check(self._lib.bgamd_env_rollout_policy(self._h, int(plies), int(top_k), float(margin)), "rollout_policy")
             try:
                 return self.rollout(states28, turn, trials, max_plies, rotate, seed, slot, position_offset, lanes, per_trial,
-                                    variance_reduction, outcomes)
+                                    variance_reduction, outcomes, groups=groups, group_offset=group_offset)
             finally:
                 _capi.check(self._lib.bgamd_env_rollout_policy(self._h, 1, 0, 0.0), "rollout_policy")
         st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
         P, T = st.shape[0], int(trials)
         t = self._dev(turn, torch.int32, (P,))
+        if groups is not None:
+            grp = torch.as_tensor(groups).to(torch.int64).reshape(-1)
+            if grp.shape[0] != P:
+                raise ValueError("rollout: groups has %d entries for %d positions" % (grp.shape[0], P))
+            if P and (int(grp.min()) < -(2 ** 31) or int(grp.max()) >= 2 ** 31):
+                raise ValueError("rollout: a group does not fit in int32")
+            grp = grp.to(torch.int32).to(self.device).contiguous()
         out = {"mean": self._buf((P,), torch.float64), "stderr": self._buf((P,), torch.float64),
                "turns": self._buf((P,), torch.int64), "truncated": self._buf((P,), torch.int32)}
         if per_trial:
             out["trial_value"] = self._buf((P, max(T, 0)), torch.float32)
             out["trial_turns"] = self._buf((P, max(T, 0)), torch.int32)
         flags = (ROLLOUT_ROTATE if rotate else 0) | (WEIGHTS_SLOT1 if slot else 0) | (ROLLOUT_VR if variance_reduction else 0)
-        _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
-                                                int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
-                                                _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
-                                                _ptr(out.get("trial_turns")), _stream()), "rollout")
+        if groups is None:
+            _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
+                                                    int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
+                                                    _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
+                                                    _ptr(out.get("trial_turns")), _stream()), "rollout")
+        else:
+            _capi.check(self._lib.bgamd_env_rollout_grouped(self._h, flags, _ptr(st), _ptr(t), _ptr(grp), P, int(group_offset), T,
+                                                            int(max_plies), int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]),
+                                                            _ptr(out["stderr"]), _ptr(out["turns"]), _ptr(out["truncated"]),
+                                                            _ptr(out.get("trial_value")), _ptr(out.get("trial_turns")), _stream()),
+                        "rollout_grouped")
         self._rollout_shape = (P, T)
         if variance_reduction:
             out["vr_mean"], out["vr_stderr"] = self._buf((P,), torch.float64), self._buf((P,), torch.float64)
@@ -434,6 +457,27 @@ class VecGame:
                                                               _ptr(out["equity_stderr"]), _ptr(out.get("trial_points")), _stream()),
                     "rollout_outcomes_read")
         return out
+
+    PAIRED_WHICH = {"value": 0, "vr": 1, "equity": 2}
+
+    def rollout_paired(self, ref, which="value"):
+        """Paired differences of the last rollout (bgamd_env_rollout_paired_read): for each position p and its reference ref[p] (an index
+        into that call's positions), mean and standard error of the per-trial differences q_i(p) - q_i(ref[p]) -- q the trial's value
+        ("value"), its luck-adjusted value ("vr": the rollout must have had variance_reduction) or its equity in points ("equity").  Only
+        positions of one dice group share dice: a reference in another group, or out of range, gives NaN for that p; after a rollout
+        without groups every ref[p] != p does.  ref[p] = p gives 0.  -> (diff_mean [P], diff_stderr [P]), float64 device tensors;
+        stream-ordered."""
+        if which not in self.PAIRED_WHICH:
+            raise ValueError("rollout_paired: which is one of 'value', 'vr', 'equity'")
+        P, _ = self._rollout_shape
+        r = torch.as_tensor(ref).to(torch.int64).reshape(-1)
+        if r.shape[0] != P:
+            raise ValueError("rollout_paired: ref has %d entries for %d positions" % (r.shape[0], P))
+        r = r.clamp(-1, 2 ** 31 - 1).to(torch.int32).to(self.device).contiguous()          # (anything out of range stays out of range)
+        dm, ds = self._buf((P,), torch.float64), self._buf((P,), torch.float64)
+        _capi.check(self._lib.bgamd_env_rollout_paired_read(self._h, _ptr(r), self.PAIRED_WHICH[which], _ptr(dm), _ptr(ds), _stream()),
+                    "rollout_paired_read")
+        return dm, ds
 
     def rollout_info(self):
         """The last rollout's [lanes, env steps issued, lane-steps of live trials, turns per run]: idle share = 1 - [2] / ([0] [1])."""

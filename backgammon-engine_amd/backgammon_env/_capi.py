@@ -73,6 +73,9 @@ SYMBOLS = [
     ("bgamd_env_analysis_read", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_rollout", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
                                     _P, _P, _P, _P, _P, _P, _P]),
+    ("bgamd_env_rollout_grouped", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
+                                            _P, _P, _P, _P, _P, _P, _P]),
+    ("bgamd_env_rollout_paired_read", C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     ("bgamd_env_rollout_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("bgamd_env_rollout_policy", C.c_int, [_P, C.c_int, C.c_int, C.c_float]),
     ("bgamd_env_evaluate_preroll", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, _P]),

@@ -63,6 +63,80 @@ def rollout_moves(env, state28, turn, dice, top_k=8, trials=1296, max_plies=0, s
     return out
 
 
+def rollout_decisions(env, top_k=8, trials=1296, max_plies=0, seed=20240603, variance_reduction=False, outcomes=False, plies=1,
+                      rollout_top_k=4, rollout_margin=float("inf"), group_offset=0):
+    """rollout_moves for every lane of an env at once: one search step, ONE rollout call over all candidates of all decisions, and the
+    paired statistics that common dice are for.
+
+    env: an n-lane VecGame with weights in slot 0.  Its lanes hold the decisions as they stand: board, side to move, set dice
+    (set_states / set_dice, or wherever play left them).  One step_search(top_k, roll=False, auto_reset=False, no_flip=True) over all
+    lanes lists every lane's kept candidates; afterwards every lane's board, side to move and dice are put back with set_states /
+    set_dice, as rollout_moves does for its one lane (last_choice / search_candidates then describe this search).
+    All kept candidates of all lanes form one position list, the opponent to move, the lane index as dice group: VecGame.rollout(groups=
+    lane, group_offset=group_offset) rolls them out in one call -- `trials` rotated trials, turn limit max_plies --, trial i of every
+    candidate of lane g on the dice of game id (group_offset + g) * trials + i.  Lane 0 at group_offset 0 therefore plays exactly the
+    trials rollout_moves plays for that decision.  plies / rollout_top_k / rollout_margin: who plays the trials, as there.
+
+    -> one list per lane, best first by the rule of rollout_moves (mean, or vr_mean under variance_reduction, for the lane's mover; ties
+    keep the search's order).  Every entry carries rollout_moves' fields -- index, seq, state, v1, v2, mean, stderr, turns, with
+    variance_reduction vr_mean, vr_stderr, with outcomes equity, equity_stderr, counts -- and, against the lane's best entry b over the
+    same trials (VecGame.rollout_paired; of the values, or of the luck-adjusted values under variance_reduction):
+      diff         mean of the per-trial differences q_i(candidate) - q_i(b): <= 0 for PLAYER1's rivals, >= 0 for PLAYER2's (up to ties);
+      diff_stderr  their standard error -- the paired one, which credits the shared dice;
+      jsd          |diff| / diff_stderr, the joint standard deviations the candidate lies behind the best: 0.0 for the best itself and
+                   where diff is 0, inf where diff_stderr is 0 and diff is not.
+    A lane whose search keeps no candidate gives an empty list.  By the search step's contract (bgamd_env_search_info: "lanes that had
+    a move" are those with kept >= 1) that is a lane whose mover has no legal move with its two different dice (a pass), and a frozen
+    lane -- a game that finished without auto_reset takes no part in any step.  A DOUBLES roll without a move is not such a lane: the
+    reference's enumeration lists one empty sequence for it, the board itself, the search keeps it, and the lane's list is that one
+    entry (seq [], the board rolled out with the opponent to move).  Every lane's board, side to move and dice are put back alike;
+    set_states lifts a frozen lane's frozen mark (flags bit 2), here as everywhere."""
+    n = env.n
+    saved = env.snapshot().cpu().numpy()
+    movers = saved[:, 28].astype(np.int64)
+    try:
+        offs, cnts, st, sq, ln = (x.cpu().numpy() for x in env.enumerate())
+        env.step_search(top_k=top_k, roll=False, auto_reset=False, no_flip=True)
+        cst, v1, v2, kept = (x.cpu().numpy() for x in env.search_candidates())
+    finally:
+        env.set_states(saved[:, :28], saved[:, 28])
+        env.set_dice(saved[:, 29:31])
+    lanes = [g for g in range(n) for _ in range(int(kept[g]))]
+    slots = [k for g in range(n) for k in range(int(kept[g]))]
+    out = [[] for _ in range(n)]
+    if not lanes:
+        return out
+    after = cst[lanes, slots]
+    r = env.rollout(after, [1 - int(movers[g]) for g in lanes], trials, max_plies=max_plies, rotate=True, seed=seed,
+                    variance_reduction=variance_reduction, outcomes=outcomes, plies=plies, top_k=rollout_top_k, margin=rollout_margin,
+                    groups=lanes, group_offset=group_offset)
+    key = "vr_mean" if variance_reduction else "mean"
+    h = {k: v.cpu().numpy() for k, v in r.items()}
+    flat = [[] for _ in range(n)]
+    for q, g in enumerate(lanes):
+        flat[g].append(q)
+    for g in range(n):                                     # (a stable sort, as rollout_moves': ties keep the search's order)
+        flat[g].sort(key=lambda q: -h[key][q] if movers[g] == 0 else h[key][q])
+    ref = [flat[g][0] for g in lanes]
+    dm, ds = (x.cpu().numpy() for x in env.rollout_paired(ref, "vr" if variance_reduction else "value"))
+    for g in range(n):
+        rows = st[offs[g]:offs[g] + cnts[g]]
+        for q in flat[g]:
+            a = after[q]
+            idx = int(offs[g]) + int(np.flatnonzero((rows == a).all(axis=1))[0])
+            c = {"index": idx - int(offs[g]), "seq": [tuple(int(x) for x in sq[idx, m]) for m in range(int(ln[idx]))], "state": a,
+                 "v1": float(v1[g, slots[q]]), "v2": float(v2[g, slots[q]]), "mean": float(h["mean"][q]),
+                 "stderr": float(h["stderr"][q]), "turns": int(h["turns"][q])}
+            if variance_reduction:
+                c.update(vr_mean=float(h["vr_mean"][q]), vr_stderr=float(h["vr_stderr"][q]))
+            if outcomes:
+                c.update(equity=float(h["equity"][q]), equity_stderr=float(h["equity_stderr"][q]), counts=[int(x) for x in h["counts"][q]])
+            d, se = float(dm[q]), float(ds[q])
+            c.update(diff=d, diff_stderr=se, jsd=0.0 if d == 0.0 else (math.inf if se == 0.0 else abs(d) / se))
+            out[g].append(c)
+    return out
+
+
 def error_rate(player, judge, turns, top_k=4, epsilon=0.0, player_slot=0, judge_slot=0, on_turn=None, temperature=None):
     """How much the player's moves lose by the judge's 2-ply search, over `turns` turns of every lane of `player`.
 

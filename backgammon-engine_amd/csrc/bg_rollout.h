@@ -21,6 +21,7 @@ constexpr uint32_t RO_TURN_MASK = (1u << RO_PTS_SHIFT) - 1u;   // 3-bit two's co
 constexpr uint32_t RO_TURN_LIMIT = 100000;           // M = 0: a trial still running after this many turns is an error
 enum { RO_NEXT = 0, RO_DONE = 1, RO_NTRUNC = 2, RO_ERR = 3, RO_CTRS = 4 };
 enum { ERRF_RO_LONG = 8, ERRF_RO_PLY = 16 };
+enum { ERRF_RO_GROUP = 256 };                        // intake word, beside ERRF_STATE: a bad group table (bg_rollout_groups.h)
 
 struct RoView {
     long long N, T, M;                                // trials in all, per position, turn limit (0 = none)
@@ -35,6 +36,7 @@ struct RoView {
     uint4 *trows;                                     // [L][2] truncated trials of this refill
     uint32_t *tids;                                   // [L]
     unsigned long long *ctr;                          // RO_*
+    const int32_t *group;                             // [P] dice group of every position (bgamd_env_rollout_grouped), NULL: its own
 };
 
 // One global atomic per workgroup: the lanes with `want` get consecutive slots of *ctr in thread order.  Every thread of the workgroup
@@ -116,7 +118,9 @@ __global__ __launch_bounds__(RO_NT) void ro_fan_collect_kernel(EnvView e, long l
 // A lane without a trial then takes the next unstarted one, trial jl = p T + i: at ply 0 from position p, or -- rotation -- at ply 1 from fan entry
 // p F + i % 36.  Trials that are over before a turn is played on a lane (a finished position: 0 turns; rotation: a first turn that
 // ended the game, or M = 1) are scored here and the lane takes the next.  The lane plays trial jl as episode jl + L - g with lane_stride 1
-// and lane_offset = base - L: game id base + jl, the dice of trial j = base + jl at every ply.
+// and lane_offset = base - L: game id base + jl, the dice of trial j = base + jl at every ply.  With a group table (r.group) the slot
+// and the dice id are two numbers: the trial's result still goes to slot jl, but it is played as episode group[p] T + i + L - g with
+// lane_offset = group_offset T - L: game id (group_offset + group[p]) T + i, the same dice for trial i of every position of a group.
 __global__ __launch_bounds__(RO_NT) void ro_refill_kernel(EnvView e, RoView r)
 {
     const long long g = (long long)blockIdx.x * RO_NT + threadIdx.x;
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(RO_NT) void ro_refill_kernel(EnvView e, RoView r)
         store_planes(e, g, p);
         e.meta[g] = meta_pack(turn, 0, 0, false);
         e.ply[g] = ply;
-        e.episode[g] = jl + (uint32_t)e.n - (uint32_t)g;
+        e.episode[g] = (r.group ? (uint32_t)r.group[pi] * (uint32_t)r.T + (uint32_t)i : jl) + (uint32_t)e.n - (uint32_t)g;
         e.flags[g] = 0;
         r.lane_trial[g] = jl;
         seated = true;

@@ -798,6 +798,9 @@ struct RolloutState {
     long long cap_vtrials = 0, cap_vlanes = 0, cap_vpos = 0;
     long long vr_P = 0, vr_T = 0;          // P, T of the last rollout if it had BGAMD_ROLLOUT_VR (0: bgamd_env_rollout_vr_read refuses)
     long long out_P = 0, out_T = 0;        // P, T of the last rollout (0: none yet, or it failed: bgamd_env_rollout_outcomes_read refuses)
+    int32_t *group = nullptr;              // [cap_group] the group table of the last bgamd_env_rollout_grouped (bgamd_env_rollout_paired_read)
+    long long cap_group = 0;
+    bool grouped = false;                  // the last rollout had a group table (false: the identity, `group` is not read)
     int read_back_ready()                  // the pinned words and the two events, created on first use
     {
         if (!host) HIPCHK(hipHostMalloc(&host, 8 * 8));
@@ -806,7 +809,7 @@ struct RolloutState {
     }
     void release()
     {
-        free_all({pos, fan, trows, fval, tval, tv, tturns, lane, tids, tluck, m0, vf, f0});
+        free_all({pos, fan, trows, fval, tval, tv, tturns, lane, tids, tluck, m0, vf, f0, group});
         if (host) hipHostFree(host);
         for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
         *this = RolloutState{};
@@ -1933,12 +1936,15 @@ static int scratch_env(bgamd_env *env, bgamd_env **which, long long want_lanes, 
 // PRECONDITION: the caller has cleared env->a_ctr[A_INTAKE] on s.  The clear is not done here because the rollout clears its own
 // counters with the same fill (see bgamd_env::a_ctr) and then one more buffer before the pack: doing it here would add a launch to
 // the rollout or reorder its launches.  The bad-state word is read into a pageable local; the synchronise below covers that copy.
-static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int32_t *d_turn, long long n, uint4 *rows, hipStream_t s)
+// h_word: the whole word as read, for a caller that had another kernel flag something in it before this call (the grouped rollout).
+static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int32_t *d_turn, long long n, uint4 *rows, hipStream_t s,
+                            unsigned long long *h_word = nullptr)
 {
     unsigned long long h = 0;
     hipLaunchKernelGGL(pack_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_turn, n, rows, &env->a_ctr[A_INTAKE]);
     HIPCHK(hipMemcpyAsync(&h, &env->a_ctr[A_INTAKE], 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (h_word) *h_word = h;
     return (h & ERRF_STATE) ? BGAMD_E_STATE : BGAMD_OK;
 }
 
@@ -1955,6 +1961,10 @@ static void launch_flt_reduce(hipStream_t s, long long n, const SearchState &se,
 static void launch_flt_info(hipStream_t s, long long n, const SearchState &se);
 // the search log's pass (bg_search_log.h): declared here and defined at the very end of the file for the same reason
 static void launch_search_log(hipStream_t s, const bgamd_env *env, int flags, uint32_t min_searched);
+// the grouped rollout's two kernels (bg_rollout_groups.h): likewise
+static void launch_ro_group_intake(hipStream_t s, const int32_t *d_group, long long P, long long T, int32_t *dst, unsigned long long *err);
+static void launch_ro_pair_reduce(hipStream_t s, const bgamd_env *env, int which, const int32_t *d_ref, double *d_diff_mean,
+                                  double *d_diff_stderr);
 
 // d_played NULL: the search step.  Else the analysis of the played afterstates d_played [n][28]: the same stages with the played row
 // matched and forced into the kept set, and in place of the choice and the apply launch the per-lane results and their summary.
@@ -2228,6 +2238,17 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
                       double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
                       float *d_trial_value, int32_t *d_trial_turns, void *stream)
 {
+    return bgamd_env_rollout_grouped(env, flags, d_states28, d_turn, nullptr, n_positions, position_offset, trials, max_plies, seed, lanes,
+                                     d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns, stream);
+}
+
+// d_group NULL: every position its own group, position p's being p -- bgamd_env_rollout with position_offset = group_offset: no group
+// table is copied or read, the launches are those of that call.
+int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, const int32_t *d_group,
+                              int64_t n_positions, int64_t position_offset /* group_offset */, int64_t trials, int64_t max_plies,
+                              uint64_t seed, int64_t lanes, double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
+                              float *d_trial_value, int32_t *d_trial_turns, void *stream)
+{
     if (env) env->ro.vr_P = 0;                         // (bgamd_env_rollout_vr_read: only after a call that had the flag)
     if (env) env->ro.out_P = 0;                        // (bgamd_env_rollout_outcomes_read: only after a call that succeeded)
     if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
@@ -2257,19 +2278,27 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
                (rc = grow_buffers(L, ro.cap_vlanes, {{(void **)&ro.vf, 4 * SRCH_ROLLS}})) ||
                (rc = grow_buffers(P, ro.cap_vpos, {{(void **)&ro.f0, 4 * SRCH_ROLLS}, {(void **)&ro.m0, 8}}))))
         return rc;
+    if (d_group && (rc = grow_buffers(P, ro.cap_group, {{(void **)&ro.group, 4}}))) return rc;
     if ((rc = ro.read_back_ready())) return rc;
     unsigned long long *h = ro.host, *ctr = env->a_ctr;
 
     // the positions as rows; a bad state is refused before anything is played
     HIPCHK(hipMemsetAsync(env->a_ctr, 0, A_WORDS * 8, s));
     HIPCHK(hipMemsetAsync(sc->v.counters, 0, C_COUNT * 8, s));
-    if ((rc = intake_positions(env, d_states28, d_turn, P, ro.pos, s))) return rc;
+    // ... and, in the same pass, a bad group table: the env's copy is written, checked, and read by nothing before the synchronise
+    unsigned long long intake = 0;
+    if (d_group) launch_ro_group_intake(s, d_group, P, T, ro.group, &env->a_ctr[A_INTAKE]);
+    rc = intake_positions(env, d_states28, d_turn, P, ro.pos, s, &intake);
+    if (intake & ERRF_RO_GROUP) return BGAMD_E_INVALID;
+    if (rc) return rc;
 
-    // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1
+    // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1.
+    // Grouped: game id (group_offset + group[p]) T + i, episode group[p] T + i + L - g (ro_refill_kernel); the slot stays jl.
     sc->v.seed = seed;
     sc->v.lane_stride = 1;
     sc->v.lane_offset = (unsigned long long)position_offset * (unsigned long long)T - (unsigned long long)L;
-    const RoView r{N, T, M, rotate ? 1 : 0, F, ro.pos, ro.fan, ro.fval, ro.lane, ro.tval, ro.tturns, ro.trows, ro.tids, ctr};
+    const RoView r{N, T, M, rotate ? 1 : 0, F, ro.pos, ro.fan, ro.fval, ro.lane, ro.tval, ro.tturns, ro.trows, ro.tids, ctr,
+                   d_group ? (const int32_t *)ro.group : nullptr};
     const int run_flags = flags & BGAMD_WEIGHTS_SLOT1;
     const StepStreams ss{s, sc->overlap ? sc->side : s, sc->n_cu};
     long long steps = 0;
@@ -2404,6 +2433,17 @@ int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, cons
     HIPCHK(hipStreamSynchronize(s));
     if (vr) { ro.vr_P = P; ro.vr_T = T; }
     ro.out_P = P; ro.out_T = T;
+    ro.grouped = d_group != nullptr;
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_paired_read(bgamd_env *env, const int32_t *d_ref, int which, double *d_diff_mean, double *d_diff_stderr, void *stream)
+{
+    ENV_GUARD(env);
+    if (env->ro.out_P < 1 || !d_ref || which < 0 || which > 2) return BGAMD_E_INVALID;
+    if (which == 1 && env->ro.vr_P < 1) return BGAMD_E_INVALID;
+    launch_ro_pair_reduce((hipStream_t)stream, env, which, d_ref, d_diff_mean, d_diff_stderr);
+    HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
 
@@ -3580,4 +3620,23 @@ static void launch_search_log(hipStream_t s, const bgamd_env *env, int flags, ui
     hipLaunchKernelGGL(srch_log_kernel<SRCH_NT>, grid1(env->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, flags, (const uint4 *)env->sv.root_rows,
                        (const unsigned long long *)env->sv.best, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows,
                        (const uint32_t *)se.c_key, (const float *)se.c_v1, (const float *)se.c_v2, min_searched, env->slog);
+}
+
+// ---- the grouped rollout's kernels (declared before search_stages; kernel templates first launched here, so that no other kernel moves) ---
+namespace {
+#include "bg_rollout_groups.h"
+}
+
+static void launch_ro_group_intake(hipStream_t s, const int32_t *d_group, long long P, long long T, int32_t *dst, unsigned long long *err)
+{
+    hipLaunchKernelGGL(ro_group_intake_kernel<128>, grid1(P, 128), dim3(128), 0, s, d_group, P, T, dst, err);
+}
+
+static void launch_ro_pair_reduce(hipStream_t s, const bgamd_env *env, int which, const int32_t *d_ref, double *d_diff_mean,
+                                  double *d_diff_stderr)
+{
+    const RolloutState &ro = env->ro;
+    hipLaunchKernelGGL(ro_pair_reduce_kernel<64>, dim3((unsigned)ro.out_P), dim3(64), 0, s, (long long)ro.out_P, (long long)ro.out_T, which,
+                       d_ref, ro.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr, (const float *)ro.tval,
+                       (const uint32_t *)ro.tturns, (const double *)ro.tluck, d_diff_mean, d_diff_stderr);
 }

@@ -398,6 +398,37 @@ int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4]);
  * plies other than 1 or 2, top_k < 0, a negative or NaN margin: BGAMD_E_INVALID (the setting is unchanged). */
 int bgamd_env_rollout_policy(bgamd_env *env, int plies /* 1 | 2 */, int top_k, float margin);
 
+/* ---- rollouts on shared dice: dice groups and paired differences -------------------------------------------------------------------------
+ * bgamd_env_rollout in every respect but the dice id.  d_group[P] assigns each position to a dice group (any non-negative numbers: sparse,
+ * unordered, repeated).  Trial i of position p rolls the TURN-stream dice of game id j = (group_offset + d_group[p]) * T + i -- trial i of
+ * every position of a group plays the same dice at every ply ("common random numbers": the candidates of one decision meet the same
+ * luck, so their difference is known far more tightly than either mean).  With BGAMD_ROLLOUT_ROTATE turn 0 uses ordered pair i mod 36, as
+ * there.  The trial's RESULT slot stays p * T + i: every output ([P], [P][T]) is indexed by position as before, and so is everything the
+ * read calls return.  Unchanged: the policy (bgamd_env_rollout_policy), BGAMD_ROLLOUT_VR, bgamd_env_rollout_outcomes_read, truncation,
+ * the fixed reduction order, bit-identical results for any `lanes`, from call to call and when the groups are split over calls with
+ * group_offset, and no side effect on the env.  Position p of this call computes, bit for bit, what the single-position call
+ * bgamd_env_rollout(position p alone, position_offset = group_offset + d_group[p]) computes.
+ * d_group NULL: every position is its own group p -- this IS bgamd_env_rollout with position_offset = group_offset (the same launches,
+ * the same bits; bgamd_env_rollout is implemented as this call).
+ * Errors, beside bgamd_env_rollout's: a negative group, (max group + 1) * T >= 2^31 or group_offset < 0: BGAMD_E_INVALID.  The table is
+ * checked in the pass that refuses bad states, before anything is played.
+ * The env keeps a device copy of the table (4 P bytes) for bgamd_env_rollout_paired_read. */
+int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, const int32_t *d_group /*[P]*/,
+                              int64_t n_positions, int64_t group_offset, int64_t trials, int64_t max_plies, uint64_t seed, int64_t lanes,
+                              double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
+                              float *d_trial_value, int32_t *d_trial_turns, void *stream);
+/* Paired differences of the last rollout of either kind (P and T of that call; BGAMD_E_INVALID before the first or after one that failed).
+ * `which` selects the per-trial quantity q: 0 the value x_i; 1 the luck-adjusted y_i = (double) x_i - L_i (BGAMD_E_INVALID unless that
+ * rollout had BGAMD_ROLLOUT_VR); 2 the equity e_i in points as bgamd_env_rollout_outcomes_read defines it.  Other values: BGAMD_E_INVALID.
+ * For each position p with its reference r = d_ref[p], in fp64:
+ *   d_i = q_i(p) - q_i(r);  d_diff_mean[p] = (1/T) sum d_i;  d_diff_stderr[p] = sqrt(sum (d_i - diff_mean)^2 / (T (T - 1))), 0 for T = 1,
+ * reduced in the fixed order of the plain statistics (one wave per position, lane k takes trials k, k + 64, ..., then the same butterfly).
+ * A reference outside [0, P), or in another dice group than p (after an ungrouped rollout: any r != p) pairs nothing: both outputs are
+ * NaN for that p, the other positions are unaffected.  r = p gives exactly 0 and 0.  Either output may be NULL; d_ref may not.
+ * Stream-ordered, does not synchronise; the rollout's own outputs and the other reads are what they were without this call. */
+int bgamd_env_rollout_paired_read(bgamd_env *env, const int32_t *d_ref /*[P]*/, int which, double *d_diff_mean /*[P]*/,
+                                  double *d_diff_stderr /*[P]*/, void *stream);
+
 /* ---- 1-ply pre-roll evaluation (GNU Backgammon's "evaluation before the roll") ------------------------------------------------------
  * For each of the n positions s = d_states28[n] with the side to roll m = d_turn[n] (NULL = PLAYER1), what the roller can expect from
  * each of the 21 unordered rolls r = (1,1), (1,2), ..., (1,6), (2,2), ..., (6,6), in that order (the search's roll order):

@@ -14,7 +14,13 @@ every record also carries the six shares (PLAYER1 single game / gammon / backgam
 positions and the mean equity of the positions in points.
 
 --plies 2 [--top-k K --margin M]: the trials are played by the filtered 2-ply search (bgamd_env_rollout_policy) instead of the greedy
-step; a 2-ply turn costs ~100 greedy steps, so give fewer --trials.  With --vr: the luck pass beside 2-ply turns."""
+step; a 2-ply turn costs ~100 greedy steps, so give fewer --trials.  With --vr: the luck pass beside 2-ply turns.
+
+--groups D,K: D decisions (mid-game positions with rolled dice whose 2-ply search keeps K candidates) of K candidates each, every
+candidate rolled out with --group-trials rotated trials, twice on the same positions, seed and trials: as ONE grouped call
+(bgamd_env_rollout_grouped, the decision as dice group) and as D x K single-position calls at position_offset = decision, which is what
+analysis.rollout_moves does.  Both in ms (median of --regions runs after a warm-up run), whether the two agree bit for bit, and the
+median over the non-best candidates of unpaired sqrt(se_a^2 + se_b^2) / paired diff_stderr against the decision's best candidate."""
 import argparse
 import json
 import os
@@ -73,6 +79,9 @@ def main():
     ap.add_argument("--plies", type=int, default=1, choices=(1, 2), help="who plays the trials: 1 = the greedy step, 2 = the filtered 2-ply search")
     ap.add_argument("--top-k", type=int, default=5, help="--plies 2: the search's top_k")
     ap.add_argument("--margin", type=float, default=0.04, help="--plies 2: the search's margin")
+    ap.add_argument("--groups", default=None, metavar="D,K", help="D decisions of K candidates: one grouped call against D x K single calls")
+    ap.add_argument("--group-trials", type=int, default=1296)
+    ap.add_argument("--max-plies", type=int, default=0, help="--groups: the turn limit of the trials (0 = to the end)")
     ap.add_argument("--configs", default="full,truncated,pair", help="which of full (M = 0), truncated (M = 7), pair (M = 0 again) to run")
     a = ap.parse_args()
     global POLICY
@@ -81,6 +90,9 @@ def main():
         ap.error("--outcomes reads the plain run's games; it is not combined with --vr")
     import backgammon_env as bg
     w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
+    if a.groups:
+        _groups(bg, w, a)
+        return
     st, tu = _positions(bg, w, a.positions, 1)
     env = bg.VecGame(a.lanes, seed=1)
     env.load_weights(w)
@@ -122,6 +134,75 @@ def main():
         out.append(rec)
     env.close()
     print(json.dumps({"rollout_bench": out}))
+
+
+def _groups(bg, w, a):
+    D, K = (int(x) for x in a.groups.split(","))
+    # decisions: mid-game positions with rolled dice; the first D whose search keeps K candidates
+    n = 4 * D + 16
+    st, tu = _positions(bg, w, n, 1)
+    dec = bg.VecGame(n, seed=2)
+    dec.load_weights(w)
+    dec.set_states(st, tu)
+    dec.set_dice(np.random.RandomState(3).randint(1, 7, (n, 2)).astype(np.int32))
+    dec.step_search(top_k=K, roll=False, auto_reset=False, no_flip=True)
+    cst, _, _, kept = (x.cpu().numpy() for x in dec.search_candidates())
+    dec.close()
+    pick = np.flatnonzero(kept == K)[:D]
+    if len(pick) < D:
+        raise SystemExit("only %d of %d decisions keep %d candidates" % (len(pick), n, K))
+    after = cst[pick].reshape(D * K, 28)
+    turn = np.repeat(1 - tu[pick], K).astype(np.int32)
+    group = np.repeat(np.arange(D), K)
+    T, M = a.group_trials, a.max_plies
+    env = bg.VecGame(64, seed=1)
+    env.load_weights(w)
+    kw = dict(max_plies=M, rotate=True, seed=5, **POLICY)
+
+    def grouped():
+        r = env.rollout(after, turn, T, groups=group, **kw)
+        best = np.empty(D * K, np.int64)
+        m = r["mean"].cpu().numpy().reshape(D, K)
+        for d in range(D):                                 # the decision's best for its mover, as analysis.rollout_decisions ranks
+            best[d * K:(d + 1) * K] = d * K + (np.argmax(m[d]) if tu[pick[d]] == 0 else np.argmin(m[d]))
+        dm, ds = env.rollout_paired(best, "value")
+        torch.cuda.synchronize()
+        return r, best, dm.cpu().numpy(), ds.cpu().numpy()
+
+    def singles():
+        out = [env.rollout(after[q:q + 1], turn[q:q + 1], T, position_offset=int(group[q]), **kw) for q in range(D * K)]
+        torch.cuda.synchronize()
+        return out
+
+    def timed(fn):
+        fn()                                               # warm-up (the trial env of this lane count, buffers)
+        ms = []
+        for _ in range(a.regions):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ms), ms, res
+
+    g_ms, g_all, (r, best, dm, ds) = timed(grouped)
+    g_info = env.rollout_info()
+    s_ms, s_all, one = timed(singles)
+    s_info = env.rollout_info()
+    mean, se = r["mean"].cpu().numpy(), r["stderr"].cpu().numpy()
+    same = all(float(one[q]["mean"][0]) == mean[q] and float(one[q]["stderr"][0]) == se[q] for q in range(D * K))
+    rival = np.flatnonzero((best != np.arange(D * K)) & (ds > 0))
+    ratio = np.sqrt(se[rival] ** 2 + se[best[rival]] ** 2) / ds[rival]
+    rec = {"decisions": D, "candidates": K, "positions": D * K, "trials": T, "max_plies": M, "plies": a.plies,
+           "grouped_ms": round(g_ms, 2), "singles_ms": round(s_ms, 2), "speedup": round(s_ms / g_ms, 2),
+           "grouped_lanes": g_info[0], "grouped_idle_share": round(1.0 - g_info[2] / float(g_info[0] * g_info[1]), 4),
+           "single_lanes": s_info[0], "single_idle_share_last": round(1.0 - s_info[2] / float(s_info[0] * s_info[1]), 4),
+           "bit_identical": bool(same), "rivals": int(len(rival)),
+           "unpaired_over_paired_stderr_median": round(float(np.median(ratio)), 3),
+           "unpaired_over_paired_stderr_min": round(float(ratio.min()), 3), "unpaired_over_paired_stderr_max": round(float(ratio.max()), 3),
+           "jsd_median": round(float(np.median(np.abs(dm[rival]) / ds[rival])), 3),
+           "grouped_regions_ms": [round(x, 2) for x in g_all], "singles_regions_ms": [round(x, 2) for x in s_all]}
+    env.close()
+    print(json.dumps({"rollout_groups_bench": rec}))
 
 
 def _timed(env, st, tu, trials, M, lanes, regions, vr):
