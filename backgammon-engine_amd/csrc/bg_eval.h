@@ -699,6 +699,8 @@ __global__ BG_DELTA_BOUNDS void eval_rows_delta_kernel(
     if (n_rows_ptr && threadIdx.x == 0) {                      // and how many tiles it worked, at the top end of the value array
         values[n_rows_imm - 1 - (long long)blockIdx.x] = (float)(wall_clock64() - wg_t0) * 0.01f;
         values[n_rows_imm - 1 - (long long)gridDim.x - (long long)blockIdx.x] = (float)s_ticket;
+        values[n_rows_imm - 1 - 10240 - (long long)blockIdx.x] = __uint_as_float((uint32_t)wg_t0);      // (absolute, low 32 bits of the 100 MHz clock:
+        values[n_rows_imm - 1 - 11264 - (long long)blockIdx.x] = __uint_as_float((uint32_t)wall_clock64());     //  the launch's span over all workgroups)
     }
 #endif
 }

@@ -4,6 +4,7 @@
 // -DBGAMD_EXPERIMENTAL: this one won its A/B.
 #pragma once
 #include "bg_eval.h"
+#include "bg_stream_store.h"
 
 namespace bg {
 
@@ -251,6 +252,88 @@ __device__ __forceinline__ int boundary_root_stage(uint4 row0, uint4 row1, long 
     return n_tiles;
 }
 
+// The tiles' MFMAs as two STAGGERED accumulator chains, the root terms stored a few at a time under them.  (Until this version: two tiles
+// side by side and their 32 stores as one block, twice -- the second block, half of the launch's 33.5 MB at 65 536 lanes, was the last thing
+// the launch did, every workgroup at the same moment.)  Two chains because with one nothing covers an MFMA chain's and an LDS read's latency
+// (a tile at a time: 2.1 us per tile and wave against 1.25).  Chain A works tiles 0, 2, ..., chain B tiles 1, 3, ..., B half a tile's K-steps
+// behind A.  When a chain ends a tile, PER of its 16 results (epilogue applied) are stored at once and the others wait in `pend`, to leave
+// over the other chain's next K-steps, PER stores per step, before that chain's own tile ends and takes `pend` over; what the launch still
+// has to store when its MFMAs end is ONE tile's results per wave.  The stores write through (bg_stream_store.h); measurements of the pacing
+// and of the store flavour: profiles/ab_kernel_tails.txt, NOTEBOOK.md.  Per accumulator nothing changes: K-step ascending, planes hi,
+// (mid,) lo, the same epilogue expression -- the same bits.  167 VGPRs, none spilled (a full 16-entry `pend`: 169, past three waves per SIMD).
+// FULL: the workgroup has all its tiles and every row of them (all but the env's last workgroup): no bounds test, and the instance is one
+// basic block.  The other instance (the env's last workgroup only) tests every tile and every store.
+// sXl = the lane's operands, hp = the lane's first output (game g0 + 4 h, unit 32 c + r), lim = the env's games from there on.
+template <bool FULL>
+__device__ __forceinline__ void broot_paced_chains(const BRootWeights &wf, int n_tiles, int lim, const uint4 *sXl, float bb, float *hp)
+{
+    constexpr int ROUNDS = (BROOT_TILES + 1) / 2, LAG = K16_STEPS / 2, NSLOT = ROUNDS * K16_STEPS + LAG, PER = (16 + LAG - 1) / LAG;
+    static_assert(2 * LAG <= K16_STEPS && PER * LAG >= 16, "a tile's stores leave before the other chain's tile ends");
+    constexpr float NL2E = -1.44269504088896340736f;
+    union WF { uint4 u; root_vec8 v; };
+    floatx16 accA = {0}, accB = {0};
+    float pend[16];                                            // (its first PER entries are never used: those results leave at once)
+    auto put = [&](int tile, int j, float v) {                 // result j of `tile` (constants once the slots are unrolled)
+        const int orow = tile * 32 + (j & 3) + 8 * (j >> 2);
+#if defined(BG_ABL_STEP) && (BG_ABL_STEP & 4)
+        if (v == 1.2345f) hp[(long long)orow * N_HID] = 0.0f;
+#else
+        if (FULL || (tile < n_tiles && orow < lim)) stream_store(hp + (long long)orow * N_HID, v);
+#endif
+    };
+    auto drain = [&](int tile, int j0) {                       // results j0 .. j0 + PER - 1 from pend
+#pragma unroll
+        for (int j = PER; j < 16; ++j)
+            if (j >= j0 && j < j0 + PER) put(tile, j, pend[j]);
+    };
+    auto finish = [&](int tile, const floatx16 &acc) {         // a chain ends a tile: the first PER results leave, the others wait in pend
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const float v = NL2E * (acc[j] + bb);
+            if (j < PER) put(tile, j, v);
+            else pend[j] = v;
+        }
+    };
+#pragma unroll
+    for (int t = 0; t < NSLOT; ++t) {
+        if (t >= K16_STEPS) {                                  // what the chain that ended a tile last left in pend
+            const int d = (t - K16_STEPS) % K16_STEPS, k2 = 2 * ((t - K16_STEPS) / K16_STEPS);
+            if (d < LAG) drain(k2, PER * (d + 1));
+            else if (d < 2 * LAG) drain(k2 + 1, PER * (d - LAG + 1));
+        }
+        const int tA = 2 * (t / K16_STEPS), sA = t % K16_STEPS;
+        const int tB = 2 * ((t - LAG) / K16_STEPS) + 1, sB = (t - LAG) % K16_STEPS;
+        const bool onA = t < ROUNDS * K16_STEPS, onB = t >= LAG && tB < BROOT_TILES;
+        if (onA && (FULL || tA < n_tiles)) {
+            if (sA == 0) accA = floatx16{0};
+            WF x;
+            x.u = sXl[tA * D16_XBUF_U4 + sA * 64];
+#pragma unroll
+            for (int p = 0; p < ROOT_PLANES; ++p) {
+                WF wv;
+                wv.u = wf.w[p][sA];
+                accA = BG_ROOT_MFMA(x.v, wv.v, accA);
+            }
+        }
+        if (onB && (FULL || tB < n_tiles)) {
+            if (sB == 0) accB = floatx16{0};
+            WF x;
+            x.u = sXl[tB * D16_XBUF_U4 + sB * 64];
+#pragma unroll
+            for (int p = 0; p < ROOT_PLANES; ++p) {
+                WF wv;
+                wv.u = wf.w[p][sB];
+                accB = BG_ROOT_MFMA(x.v, wv.v, accB);
+            }
+        }
+        if (onA && sA == K16_STEPS - 1 && (FULL || tA < n_tiles)) finish(tA, accA);      // (a tile the workgroup does not have was not computed)
+        if (onB && sB == K16_STEPS - 1 && (FULL || tB < n_tiles)) finish(tB, accB);
+    }
+    if (2 * ROUNDS <= BROOT_TILES)                             // chain B's last tile: the launch's tail
+#pragma unroll
+        for (int j0 = PER; j0 < 16; j0 += PER) drain(2 * ROUNDS - 1, j0);
+}
+
 __device__ __forceinline__ void boundary_root_compute(const BRootWeights &wf, int n_tiles, long long g0, long long n_games,
                                                       const float *__restrict__ b1, float *__restrict__ hidden)
 {
@@ -258,43 +341,17 @@ __device__ __forceinline__ void boundary_root_compute(const BRootWeights &wf, in
     uint4 *sX = sBR;
     const int lane = threadIdx.x & 63, c = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int r = lane & 31, h = lane >> 5;
-    constexpr float NL2E = -1.44269504088896340736f;
     const float bb = b1[32 * c + r];
     __syncthreads();
-    union WF { uint4 u; root_vec8 v; };
-    // two tiles per iteration: two independent accumulator chains and twice the LDS reads in flight -- with ONE wave per SIMD nothing else
-    // covers an MFMA chain's and an LDS read's latency (a tile at a time: 2.1 us per tile and wave against 1.25 in the stand-alone kernel,
-    // whose two workgroups per CU cover each other).  Per accumulator the sequence is unchanged: K-step ascending, planes hi, mid, lo.
 #if defined(BG_ABL_STEP) && (BG_ABL_STEP & 2)
     if (n_tiles > 100)
 #endif
-    for (int tile = 0; tile < n_tiles; tile += 2) {
-        floatx16 acc0 = {0}, acc1 = {0};
-        const uint4 *xp0 = sX + tile * D16_XBUF_U4 + lane;
-        const uint4 *xp1 = sX + (tile + 1 < n_tiles ? tile + 1 : tile) * D16_XBUF_U4 + lane;
-#pragma unroll
-        for (int s = 0; s < K16_STEPS; ++s) {
-            WF x0, x1;
-            x0.u = xp0[s * 64];
-            x1.u = xp1[s * 64];
-#pragma unroll
-            for (int p = 0; p < ROOT_PLANES; ++p) {
-                WF wv;
-                wv.u = wf.w[p][s];
-                acc0 = BG_ROOT_MFMA(x0.v, wv.v, acc0);
-                acc1 = BG_ROOT_MFMA(x1.v, wv.v, acc1);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const long long orow = g0 + tile * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
-#if defined(BG_ABL_STEP) && (BG_ABL_STEP & 4)
-            if (acc0[j] == 1.2345f || acc1[j] == 1.2345f) hidden[orow * N_HID + 32 * c + r] = 0.0f;
-#else
-            if (orow < n_games) hidden[orow * N_HID + 32 * c + r] = NL2E * (acc0[j] + bb);
-            if (tile + 1 < n_tiles && orow + 32 < n_games) hidden[(orow + 32) * N_HID + 32 * c + r] = NL2E * (acc1[j] + bb);
-#endif
-        }
+    {
+        const long long left = n_games - g0 - 4 * h;
+        const int lim = left > BROOT_GPW ? BROOT_GPW : (int)left;
+        float *hp = hidden + (g0 + 4 * h) * N_HID + 32 * c + r;
+        if (n_tiles == BROOT_TILES && g0 + BROOT_GPW <= n_games) broot_paced_chains<true>(wf, n_tiles, lim, sX + lane, bb, hp);
+        else broot_paced_chains<false>(wf, n_tiles, lim, sX + lane, bb, hp);
     }
 }
 

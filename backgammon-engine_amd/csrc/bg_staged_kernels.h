@@ -630,6 +630,7 @@ __global__ __launch_bounds__(XALL_NT, 4) void expand_all_kernel(EnvView e, Stage
 #ifdef BG_EVAL_WGCLOCK
     const unsigned long long xall_t0 = wall_clock64();
     if (threadIdx.x == 0) for (int k = 0; k < 8; ++k) e.values[e.cap - 1 - 4096 - (long long)blockIdx.x * 8 - k] = 0.0f;
+    if (threadIdx.x == 0) e.values[e.cap - 1 - 8192 - (long long)blockIdx.x] = __uint_as_float((uint32_t)xall_t0);      // (absolute: see boundary_kernel)
 #endif
     // (the launch's three statistics as 32-bit per-thread accumulators: as 64-bit ones they held six VGPRs for the whole launch in a kernel built at its
     //  register cap; a workgroup stages a few thousand rows at most)
@@ -740,6 +741,7 @@ __global__ __launch_bounds__(XALL_NT, 4) void expand_all_kernel(EnvView e, Stage
 #ifdef BG_EVAL_WGCLOCK                                         // diagnostic build (tools/eval_wg_clock.py): when each workgroup ended, us after it started, and its rows
         e.values[e.cap - 1 - 1024 - (long long)blockIdx.x] = (float)(wall_clock64() - xall_t0) * 0.01f;
         e.values[e.cap - 1 - 2048 - (long long)blockIdx.x] = (float)staged_total;
+        e.values[e.cap - 1 - 9216 - (long long)blockIdx.x] = __uint_as_float((uint32_t)wall_clock64());
 #endif
     }
 }
@@ -832,6 +834,10 @@ __global__ __launch_bounds__(LANE_NT, 2) void boundary_kernel(EnvView e, StagedV
                                                            const float *__restrict__ b1)
 {
     static_assert(!ROOT || LANE_NT == BROOT_THREADS, "the in-launch root pass is written for 256-thread workgroups");
+#ifdef BG_EVAL_WGCLOCK                                         // diagnostic build (tools/eval_wg_clock.py): thread 0's first and last instruction on the
+    if (threadIdx.x == 0)                                      // 100 MHz clock (its low 32 bits, as the float's bits), at the unused top end of the value array
+        e.values[e.cap - 1 - 12288 - (long long)blockIdx.x] = __uint_as_float((uint32_t)wall_clock64());
+#endif
     // with the root pass a workgroup owns BROOT_GPW games (the threads past them idle through the lane-per-game halves: g = n is no lane of the env)
     constexpr int GPW = ROOT ? BROOT_GPW : LANE_NT;
     const long long g = (int)threadIdx.x < GPW ? (long long)blockIdx.x * GPW + threadIdx.x : e.n;
@@ -854,4 +860,7 @@ __global__ __launch_bounds__(LANE_NT, 2) void boundary_kernel(EnvView e, StagedV
     roots_collect(e, sv_next, P);
 #endif
     if (ROOT) boundary_root_compute(wf, n_tiles, (long long)blockIdx.x * GPW, e.n, b1, sv_next.root_hidden);
+#ifdef BG_EVAL_WGCLOCK                                         // (the stores issued before it may still be on their way: that is what the stamp is for)
+    if (threadIdx.x == 0) e.values[e.cap - 1 - 13312 - (long long)blockIdx.x] = __uint_as_float((uint32_t)wall_clock64());
+#endif
 }

@@ -37,5 +37,19 @@ for rep in range(5):
         m = pp[sl].mean(0)
         print("   expand_all %s workgroups, thread 0's time per stage (us, summed over the phases): node logic %.1f  scan + table %.1f  allocation %.1f  successors %.1f  (sum %.1f)"
               % (name, m[0], m[1], m[2], m[3], m.sum()), flush=True)
+    # every launch's span over its workgroups: thread 0's first and last instruction on the 100 MHz clock (low 32 bits, stored as the
+    # float's bits).  The kernel trace's duration minus this span is what the launch spends before its first and after its last wave --
+    # the tail is where the stores still on their way drain (profiles/ab_kernel_tails.txt).  The boundary launch's stamps are those of
+    # the step before the run's last one (which closes with apply_kernel).
+    av = torch.empty((14336,), dtype=torch.float32, device="cuda")
+    _capi.check(env._lib.bgamd_env_unique_rows_read(env._h, cap - 14336, 14336, None, C.c_void_p(av.data_ptr()), None), "read")
+    torch.cuda.synchronize()
+    ab = av.cpu().numpy().view(np.uint32)[::-1]          # ab[k] = bits of values[cap - 1 - k]
+    for name, off, nwg in (("expand_all_kernel", 8192, 512), ("eval_rows_delta_kernel", 10240, G), ("boundary_kernel<true>", 12288, n // 128)):
+        t0, t1 = ab[off:off + nwg].astype(np.int64), ab[off + 1024:off + 1024 + nwg].astype(np.int64)
+        first = t0.min()
+        d0, d1 = ((t0 - first) & 0xFFFFFFFF) * 0.01, ((t1 - first) & 0xFFFFFFFF) * 0.01
+        print("   %-24s workgroups' span: last end %.2f us after the first start (starts spread over %.2f us; ends: median %.2f, the last 10 %% from %.2f)"
+              % (name, d1.max(), d0.max(), np.median(d1), np.percentile(d1, 90)), flush=True)
     print("step %d: workgroup run time us: min %.1f mean %.1f max %.1f (max - mean %.1f, sigma %.2f); tiles drawn per workgroup: min %d mean %.1f max %d; corr(time, tiles) %.2f"
           % (rep, us.min(), us.mean(), us.max(), us.max() - us.mean(), us.std(), tiles.min(), tiles.mean(), tiles.max(), np.corrcoef(us, tiles)[0, 1]), flush=True)
