@@ -19,7 +19,6 @@
 #include <queue>
 #include <algorithm>
 #include <initializer_list>
-#include <utility>
 #include <dlfcn.h>
 #include <rccl/rccl.h>          // types and prototypes only: the library is resolved at run time (rccl_api below), libbgamd.so does not link it
 
@@ -669,10 +668,25 @@ static thread_local std::string g_hip_err;
         HIPCHK(hipSetDevice((env)->device));             \
     } while (0)
 
+// Device memory has ONE owner per handle (bgamd_env::mem, bgamd_td::mem; bg_devmem.h): a new buffer is a pointer member and one
+// allocation call on it, and destroy frees what was handed out.  This backend holds the file's only spellings of the four HIP calls.
+#include "bg_devmem.h"
 namespace {
+struct HipMemBackend {
+    static int done(hipError_t e, const char *call, const char *name)
+    {
+        if (e != hipSuccess) g_hip_err = std::string(call) + "(" + name + "): " + hipGetErrorString(e);
+        return e == hipSuccess ? BGAMD_OK : BGAMD_E_HIP;
+    }
+    int alloc(void **p, size_t bytes, const char *name) { return done(hipMalloc(p, bytes), "hipMalloc", name); }
+    int alloc_pinned(void **p, size_t bytes, const char *name) { return done(hipHostMalloc(p, bytes), "hipHostMalloc", name); }
+    void free(void *p) { hipFree(p); }
+    void free_pinned(void *p) { hipHostFree(p); }
+};
+using DevMem = DevMemOwner<HipMemBackend>;
+
 // The value net's device tables: per weight slot (head-to-head: one per side) the raw weights and every layout of W1 a kernel reads,
-// and the two count LUTs.  NET_TABLES is the one list of them: allocation and freeing walk it, and an env that borrows another's
-// tables (scratch_env) takes them by assigning the struct.
+// and the two count LUTs.  An env that borrows another's tables (scratch_env) takes them by assigning the struct; it never owned them.
 struct NetTables {
     float *d_w[2] = {nullptr, nullptr};    // raw weights 25601
     float4 *d_wl[2] = {nullptr, nullptr};  // fp32 MFMA layout [99][64]
@@ -693,45 +707,22 @@ struct NetTables {
     const uint4 *root_w(int slot) const { return ROOT_F16X2 ? d_wr2[slot] : d_wl3[slot]; }    // the root pass's W1 planes and LUT (bg_root_resident.h)
     const uint2 *root_lut() const { return ROOT_F16X2 ? d_lut16 : d_lut; }
 };
-// (member, pointers in it, bytes of device memory behind each).  Every member above is an array of plain device pointers (or one), so the
-// walk below treats each as void *[count].  A new table needs its member above AND its line here: one left out of this list is never
-// allocated and stays null, which its first kernel trips over at once -- not a stale copy, not a double free.  d_wm and d_wd16 are
-// members in both builds but listed, and so allocated, in the experimental build only: its kernels are their only readers.
-static const struct { size_t offset; int count; size_t bytes; } NET_TABLES[] = {
-    {offsetof(NetTables, d_w), 2, N_PARAMS * 4},           {offsetof(NetTables, d_wl), 2, EVAL_LDS_BYTES},
-    {offsetof(NetTables, d_wt), 2, DELTA_W_FLOATS * 4},    {offsetof(NetTables, d_wl3), 2, 3 * EVAL16_W_BYTES},
-    {offsetof(NetTables, d_wr2), 2, 2 * EVAL16_W_BYTES},   {offsetof(NetTables, d_wl16), 2, EVAL16_W_BYTES},
-    {offsetof(NetTables, d_wlx2), 2, EVAL16X2_W_BYTES},    {offsetof(NetTables, d_lut16), 1, EVAL16_LUT_BYTES},
-    {offsetof(NetTables, d_lut), 1, EVAL16_LUT_BYTES},
+// Fresh tables for an env that has its own: the list of (pointer, bytes), all or none.  A new table is its member above and its line
+// here: one left out is never allocated and stays null, which its first kernel trips over at once.  d_wm and d_wd16 are members in both
+// builds but listed, and so allocated, in the experimental build only: its kernels are their only readers.
+static int net_tables_alloc(DevMem &mem, NetTables &t)
+{
+#define BOTH(member, bytes) BG_BUF(t.member[0], bytes), BG_BUF(t.member[1], bytes)
+    return mem.alloc_group({
+        BOTH(d_w, N_PARAMS * 4),            BOTH(d_wl, EVAL_LDS_BYTES),         BOTH(d_wt, DELTA_W_FLOATS * 4),
+        BOTH(d_wl3, 3 * EVAL16_W_BYTES),    BOTH(d_wr2, 2 * EVAL16_W_BYTES),    BOTH(d_wl16, EVAL16_W_BYTES),
+        BOTH(d_wlx2, EVAL16X2_W_BYTES),     BG_BUF(t.d_lut16, EVAL16_LUT_BYTES), BG_BUF(t.d_lut, EVAL16_LUT_BYTES),
 #ifdef BGAMD_EXPERIMENTAL
-    {offsetof(NetTables, d_wm), 2, MD_W_BYTES},            {offsetof(NetTables, d_wd16), 2, EVAL16X2_W_BYTES},
+        BOTH(d_wm, MD_W_BYTES),             BOTH(d_wd16, EVAL16X2_W_BYTES),
 #endif
-};
-// allocate (fresh tables) or free them all, and forget them
-static int net_tables(NetTables &t, bool allocate)
-{
-    for (const auto &d : NET_TABLES)
-        for (void **p = (void **)((char *)&t + d.offset), **end = p + d.count; p < end; ++p) {
-            if (allocate) HIPCHK(hipMalloc(p, d.bytes));
-            else if (*p) hipFree(*p);
-        }
-    if (!allocate) t = NetTables{};
-    return BGAMD_OK;
+    });
+#undef BOTH
 }
-
-// Buffers that grow on demand: `need` elements of elem_bytes each in every one of bufs (freed and allocated anew when cap is below it)
-using BufList = std::initializer_list<std::pair<void **, size_t>>;      // (pointer, bytes per element)
-static int alloc_buffers(long long n, BufList bufs) { for (auto &b : bufs) HIPCHK(hipMalloc(b.first, (size_t)n * b.second)); return BGAMD_OK; }
-static int grow_buffers(long long need, long long &cap, BufList bufs)
-{
-    if (need <= cap) return BGAMD_OK;
-    for (auto &b : bufs) { if (*b.first) HIPCHK(hipFree(*b.first)); *b.first = nullptr; }
-    cap = 0;
-    if (int rc = alloc_buffers(need, bufs)) return rc;
-    cap = need;
-    return BGAMD_OK;
-}
-static void free_all(std::initializer_list<void *> ptrs) { for (void *p : ptrs) if (p) hipFree(p); }
 
 // 2-ply search (bgamd_env_step_search, bg_search.h)
 struct SearchState {
@@ -752,7 +743,6 @@ struct SearchState {
     hipStream_t stream = nullptr;
     bool info_read = false;
     int64_t info[4] = {0, 0, 0, 0};
-    void release() { free_all({cnt, off, fill, kept, koff, max, grp, rank, c_rows, c_key, c_v1, c_v2, c_rval, skept, soff, vmap, d_info}); *this = SearchState{}; }
 };
 
 // search log (bgamd_env_set_search_log, bg_search_log.h): the caller's buffers, [plies][n] each; rows NULL = no log
@@ -767,21 +757,6 @@ struct AnalysisState {
     AnaView v{};
     double *summary = nullptr;             // [ANA_SUMMARY]
     bool ready = false;                    // an analysis has run and nothing has failed since (bgamd_env_analysis_read)
-    int allocate(long long n)
-    {
-        release();                                         // (what an allocation that failed half-way left)
-        if (int rc = alloc_buffers(n, {{(void **)&v.status, 4}, {(void **)&v.distinct, 4}, {(void **)&v.rank1, 4}, {(void **)&v.rank2, 4},
-                                       {(void **)&v.v1_played, 4}, {(void **)&v.v1_best, 4}, {(void **)&v.v2_played, 4}, {(void **)&v.v2_best, 4},
-                                       {(void **)&v.error, 4}, {(void **)&v.best, 32}, {(void **)&v.ppos, 4}, {(void **)&v.pslot, 4}}))
-            return rc;
-        HIPCHK(hipMalloc(&summary, ANA_SUMMARY * 8));       // last: summary != NULL says that every buffer is there
-        return BGAMD_OK;
-    }
-    void release()
-    {
-        free_all({v.status, v.distinct, v.rank1, v.rank2, v.v1_played, v.v1_best, v.v2_played, v.v2_best, v.error, v.best, v.ppos, v.pslot, summary});
-        *this = AnalysisState{};
-    }
 };
 
 // Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h), and what the luck-adjusted ones add (bg_vr.h)
@@ -801,19 +776,6 @@ struct RolloutState {
     int32_t *group = nullptr;              // [cap_group] the group table of the last bgamd_env_rollout_grouped (bgamd_env_rollout_paired_read)
     long long cap_group = 0;
     bool grouped = false;                  // the last rollout had a group table (false: the identity, `group` is not read)
-    int read_back_ready()                  // the pinned words and the two events, created on first use
-    {
-        if (!host) HIPCHK(hipHostMalloc(&host, 8 * 8));
-        for (hipEvent_t &e : ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        return BGAMD_OK;
-    }
-    void release()
-    {
-        free_all({pos, fan, trows, fval, tval, tv, tturns, lane, tids, tluck, m0, vf, f0, group});
-        if (host) hipHostFree(host);
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-        *this = RolloutState{};
-    }
 };
 
 // pre-roll evaluation (bgamd_env_evaluate_preroll, bg_vr.h)
@@ -821,7 +783,6 @@ struct PrerollState {
     uint4 *rows = nullptr;                 // [cap] the positions
     float *f = nullptr;                    // [cap][21]
     long long cap = 0;
-    void release() { free_all({rows, f}); *this = PrerollState{}; }
 };
 
 enum { A_INTAKE = RO_CTRS, A_WORDS = RO_CTRS + 2 };      // bgamd_env::a_ctr
@@ -829,6 +790,7 @@ enum { A_INTAKE = RO_CTRS, A_WORDS = RO_CTRS + 2 };      // bgamd_env::a_ctr
 
 struct bgamd_env {
     int device = 0;
+    DevMem mem;                            // owns every block of device (and pinned) memory the members below point at
     EnvView v{};
     StagedView sv{};
     RandomView rv{};
@@ -847,7 +809,7 @@ struct bgamd_env {
     long long traj_step = 0;
     int32_t *d_scalar = nullptr;           // device staging of the scalar (host-argument) surface: args at [0..63], results behind
     void *d_tmp = nullptr;                 // ... and of its enumerate call (states | seq | len), grown on demand
-    size_t tmp_bytes = 0;
+    long long tmp_bytes = 0;
     int choice[4] = {0, 0, 0, 0};           // kernels of the last greedy step (bgamd_env_kernel_choice)
     bool list_shards = true;               // the roots' node lists in LIST_SHARDS parts (BGAMD_LIST_SHARDS=0: one list each)
     bool split_arena = true;               // the greedy step (incremental value net) keeps hit-free rows and the others in two arenas (BGAMD_SPLIT_ARENA=0: one)
@@ -874,9 +836,8 @@ struct bgamd_env {
     double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // The analysis features run the greedy step's kernels on internal envs (scratch_env): `scratch` holds the virtual roots the 2-ply search
-    // and the pre-roll evaluation score, `rscratch` plays the rollout's trials.  Such an env borrows_weights: its `net` is its parent's.
+    // and the pre-roll evaluation score, `rscratch` plays the rollout's trials.  Such an env has no tables of its own: its `net` is its parent's.
     bgamd_env *scratch = nullptr, *rscratch = nullptr;
-    bool borrows_weights = false;
     // [A_WORDS]: the rollout's counters (RoView::ctr), then the word that takes the bad-state bit of intake_positions -- one allocation, a
     // whole number of 16-byte units, so that the rollout's one fill launch clears both.  48 bytes, allocated with every env (env_allocate).
     unsigned long long *a_ctr = nullptr;
@@ -977,7 +938,7 @@ int bgamd_device_count(void)
 }
 
 static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
-                        int64_t arena_rows);
+                        int64_t arena_rows, bool borrows_weights);
 
 static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
                       int64_t arena_rows, bool borrows_weights);
@@ -1002,15 +963,11 @@ static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t see
     bgamd_env *env = new bgamd_env();
     env->device = device;
     env->n_cu = prop.multiProcessorCount;
-    env->borrows_weights = borrows_weights;
-    int rc = env_allocate(env, n_games, seed, lane_offset, lane_stride, arena_rows);
+    // the one way out after a failure: the env goes, with whatever it had allocated, and the text of the failure (a copy) stays
+    auto fail = [env](int rc, std::string why) { bgamd_env_destroy(env); g_hip_err = why; return rc; };
+    int rc = env_allocate(env, n_games, seed, lane_offset, lane_stride, arena_rows, borrows_weights);
     if (rc == BGAMD_OK) rc = bgamd_env_reset(env, nullptr);
-    if (rc != BGAMD_OK) {                       // free whatever was allocated before the failure
-        const std::string why = g_hip_err;
-        bgamd_env_destroy(env);
-        g_hip_err = why;
-        return rc;
-    }
+    if (rc != BGAMD_OK) return fail(rc, g_hip_err);
 #ifdef BGAMD_EXPERIMENTAL
     // every BGAMD_* switch reads the same way: set and atoi() != 0 (bench.py mirrors it through bgamd_env_kernel_choice, not the environment)
     auto on = [](const char *name) { const char *v = getenv(name); return v != nullptr && atoi(v) != 0; };
@@ -1052,17 +1009,14 @@ static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t see
 #endif
     if (hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&env->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&env->ev_join, hipEventDisableTiming) != hipSuccess) {
-        g_hip_err = "side stream / events";
-        bgamd_env_destroy(env);
-        return BGAMD_E_HIP;
-    }
+        hipEventCreateWithFlags(&env->ev_join, hipEventDisableTiming) != hipSuccess)
+        return fail(BGAMD_E_HIP, "side stream / events");
     *out = env;
     return BGAMD_OK;
 }
 
 static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t lane_offset, uint64_t lane_stride,
-                        int64_t arena_rows)
+                        int64_t arena_rows, bool borrows_weights)
 {
     EnvView &v = env->v;
     v.n = n_games; v.seed = seed; v.lane_offset = lane_offset; v.lane_stride = lane_stride ? lane_stride : (uint64_t)n_games;
@@ -1070,15 +1024,14 @@ static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t
     if (cap < 65536) cap = 65536;
     if (cap > (1ll << 31) - 64) cap = (1ll << 31) - 64;
     v.cap = cap;
-    const size_t n = (size_t)n_games;
-    if (int rc = alloc_buffers(n_games, {{(void **)&v.planes, 8 * 4}, {(void **)&v.meta, 4}, {(void **)&v.ply, 4}, {(void **)&v.episode, 4},   // per lane
-                                        {(void **)&v.flags, 4}, {(void **)&v.cand_off, 4}, {(void **)&v.cand_cnt, 4}, {(void **)&v.chosen, 4},
-                                        {(void **)&v.chosen_seq, 4}, {(void **)&v.chosen_val, 4}})) return rc;
-    if (int rc = alloc_buffers(cap, {{(void **)&v.rows, 32}, {(void **)&v.seqs, 4}, {(void **)&v.values, 4}})) return rc;                  // per arena row
-    HIPCHK(hipMalloc(&v.counters, C_COUNT * 8));
-    HIPCHK(hipMalloc(&env->a_ctr, A_WORDS * 8));
-    if (!env->borrows_weights)
-        if (int rc = net_tables(env->net, true)) return rc;
+    const size_t n = (size_t)n_games, rows = (size_t)cap;
+    if (int rc = env->mem.alloc_group({BG_BUF(v.planes, n * 8 * 4), BG_BUF(v.meta, n * 4), BG_BUF(v.ply, n * 4), BG_BUF(v.episode, n * 4),             // per lane
+                                  BG_BUF(v.flags, n * 4), BG_BUF(v.cand_off, n * 4), BG_BUF(v.cand_cnt, n * 4), BG_BUF(v.chosen, n * 4),
+                                  BG_BUF(v.chosen_seq, n * 4), BG_BUF(v.chosen_val, n * 4),
+                                  BG_BUF(v.rows, rows * 32), BG_BUF(v.seqs, rows * 4), BG_BUF(v.values, rows * 4),                                 // per arena row
+                                  BG_BUF(v.counters, C_COUNT * 8), BG_BUF(env->a_ctr, A_WORDS * 8)})) return rc;
+    if (!borrows_weights)
+        if (int rc = net_tables_alloc(env->mem, env->net)) return rc;
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_f16x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL16X2_LDS_TOTAL));
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL16_LDS_TOTAL));
     {   // staged greedy step (bg_staged.h): node lists, per-workgroup staging, unique arena
@@ -1087,35 +1040,27 @@ static int env_allocate(bgamd_env *env, int64_t n_games, uint64_t seed, uint64_t
         sv.cap_d1 = ng * 15 < 4096 ? 4096 : ng * 15;
         sv.cap_d2 = ng * 64 < 4096 ? 4096 : ng * 64;
         sv.cap_f = ng * 256 < 16384 ? 16384 : ng * 256;
+        sv.cap_f2 = sv.cap_f;
         sv.cap_rows = cap;
         sv.b_base = 0;
         sv.shards = 1;
-        HIPCHK(hipMalloc(&sv.d1, (size_t)sv.cap_d1 * sizeof(Node)));
-        HIPCHK(hipMalloc(&sv.d2, (size_t)sv.cap_d2 * sizeof(Node)));
-        HIPCHK(hipMalloc(&sv.f, (size_t)sv.cap_f * sizeof(Node)));
-        sv.cap_f2 = sv.cap_f;
-        HIPCHK(hipMalloc(&sv.f2, (size_t)sv.cap_f2 * sizeof(Node)));
-        HIPCHK(hipMalloc(&sv.u_rows, (size_t)cap * 32));
-        HIPCHK(hipMalloc(&sv.u_info, (size_t)cap * sizeof(uint2)));
-        // an overflowing step (flagged, raised by stats) leaves holes in the arena: they must name a valid game
-        HIPCHK(hipMemset(sv.u_rows, 0, (size_t)cap * 32));
-        HIPCHK(hipMemset(sv.u_info, 0, (size_t)cap * sizeof(uint2)));
-        HIPCHK(hipMalloc(&sv.best, n * 8));
-        HIPCHK(hipMalloc(&sv.root_rows, n * 32));
-        HIPCHK(hipMalloc(&sv.root_hidden, n * N_HID * 4));
-        HIPCHK(hipMalloc(&sv.tops, 2 * T_COUNT * 8));             // two sets: consecutive steps of a run alternate
-        HIPCHK(hipMemset(sv.tops, 0, 2 * T_COUNT * 8));
+        RandomView &rv = env->rv;                    // bounded random-policy step (bg_random_kernels.h): own task list and counter -- a step
+        rv.cap = sv.cap_f;                           // boundary of a multi-step run reads the tasks while the next roots write sv.f
+        if (int rc = env->mem.alloc_group({BG_BUF(sv.d1, (size_t)sv.cap_d1 * sizeof(Node)), BG_BUF(sv.d2, (size_t)sv.cap_d2 * sizeof(Node)),
+                                      BG_BUF(sv.f, (size_t)sv.cap_f * sizeof(Node)), BG_BUF(sv.f2, (size_t)sv.cap_f2 * sizeof(Node)),
+                                      BG_BUF(sv.u_rows, rows * 32), BG_BUF(sv.u_info, rows * sizeof(uint2)),
+                                      BG_BUF(sv.best, n * 8), BG_BUF(sv.root_rows, n * 32), BG_BUF(sv.root_hidden, n * N_HID * 4),
+                                      BG_BUF(sv.tops, 2 * T_COUNT * 8),         // two sets: consecutive steps of a run alternate
+                                      BG_BUF(rv.tasks, (size_t)rv.cap * sizeof(Node)), BG_BUF(rv.top, 8),
+                                      BG_BUF(rv.task_count, (size_t)rv.cap * 4), BG_BUF(rv.task_off, n * 4), BG_BUF(rv.task_n, n * 4),
+                                      BG_BUF(env->spread, n * 5 * 4)})) return rc;
         env->tops_base = sv.tops;
-        RandomView &rv = env->rv;                    // bounded random-policy step (bg_random_kernels.h)
-        rv.cap = sv.cap_f;                           // own task list and counter: a step boundary of a multi-step run
-        HIPCHK(hipMalloc(&rv.tasks, (size_t)rv.cap * sizeof(Node)));   // reads the tasks while the next roots write sv.f
-        HIPCHK(hipMalloc(&rv.top, 8));
+        // an overflowing step (flagged, raised by stats) leaves holes in the arena: they must name a valid game
+        HIPCHK(hipMemset(sv.u_rows, 0, rows * 32));
+        HIPCHK(hipMemset(sv.u_info, 0, rows * sizeof(uint2)));
+        HIPCHK(hipMemset(sv.tops, 0, 2 * T_COUNT * 8));
         HIPCHK(hipMemset(rv.top, 0, 8));
-        HIPCHK(hipMalloc(&rv.task_count, (size_t)rv.cap * 4));
-        HIPCHK(hipMalloc(&rv.task_off, n * 4));
-        HIPCHK(hipMalloc(&rv.task_n, n * 4));
     }
-    HIPCHK(hipMalloc(&env->spread, (size_t)n_games * 5 * 4));
     HIPCHK(hipMemset(v.counters, 0, C_COUNT * 8));
     HIPCHK(hipFuncSetAttribute((const void *)eval_rows_f32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_TOTAL));
 #ifdef BGAMD_EXPERIMENTAL
@@ -1134,22 +1079,11 @@ int bgamd_env_destroy(bgamd_env *env)
 {
     ENV_GUARD(env);
     hipDeviceSynchronize();
-    if (env->scratch) bgamd_env_destroy(env->scratch);
+    if (env->scratch) bgamd_env_destroy(env->scratch);            // (on this device too; each frees what its own owner handed out)
     if (env->rscratch) bgamd_env_destroy(env->rscratch);
-    HIPCHK(hipSetDevice(env->device));
-    if (!env->borrows_weights) net_tables(env->net, false);        // (a scratch env's are its parent's)
-    env->srch.release();
-    env->ana.release();
-    env->ro.release();
-    env->pre.release();
-    const EnvView &v = env->v;
-    const StagedView &sv = env->sv;
-    free_all({v.planes, v.meta, v.ply, v.episode, v.flags, v.cand_off, v.cand_cnt, v.chosen, v.chosen_seq, v.chosen_val, v.rows, v.seqs,
-              v.values, v.counters, env->a_ctr, sv.root_rows, sv.root_hidden, sv.d1, sv.d2, sv.f, sv.f2, sv.u_rows, sv.u_info, sv.best,
-              env->tops_base, env->rv.tasks, env->rv.top, env->rv.task_count, env->rv.task_off, env->rv.task_n, env->d_scalar, env->d_tmp, env->spread, env->smp_words, env->smp_score});
+    env->mem.release_all();
     for (hipEvent_t e : env->ev) hipEventDestroy(e);
-    if (env->ev_fork) hipEventDestroy(env->ev_fork);
-    if (env->ev_join) hipEventDestroy(env->ev_join);
+    for (hipEvent_t e : {env->ev_fork, env->ev_join, env->ro.ev[0], env->ro.ev[1]}) if (e) hipEventDestroy(e);
     if (env->side) hipStreamDestroy(env->side);
     delete env;
     return BGAMD_OK;
@@ -1161,7 +1095,6 @@ int bgamd_env_reset(bgamd_env *env, void *stream)
 {
     ENV_GUARD(env);
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(env->device));
     hipLaunchKernelGGL(reset_kernel, grid1(env->v.n, 256), dim3(256), 0, s, env->v, (const int32_t *)nullptr, 0u);
     HIPCHK(hipMemsetAsync(env->v.counters, 0, C_COUNT * 8, s));
     HIPCHK(hipGetLastError());
@@ -1236,8 +1169,7 @@ static int scalar_guard(bgamd_env *env)
 {
     if (!env || env->v.n != 1) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
-    if (!env->d_scalar) HIPCHK(hipMalloc(&env->d_scalar, 1024 * 4));
-    return BGAMD_OK;
+    return env->d_scalar ? BGAMD_OK : env->mem.alloc(BG_BUF(env->d_scalar, 1024 * 4));
 }
 
 int bgamd_game_snapshot(bgamd_env *env, int32_t h_out[32])
@@ -1325,13 +1257,7 @@ int64_t bgamd_game_enumerate(bgamd_env *env, int player, int d1, int d2, int32_t
     const long long C = (long long)hc[C_ARENA_TOP];
     const long long m = C < cap ? C : cap;
     if (m > 0 && (h_states28 || h_seq || h_len)) {
-        const size_t need = (size_t)m * (28 * 4 + 8 + 4);
-        if (need > env->tmp_bytes) {
-            if (env->d_tmp) hipFree(env->d_tmp);
-            env->d_tmp = nullptr; env->tmp_bytes = 0;
-            HIPCHK(hipMalloc(&env->d_tmp, need));
-            env->tmp_bytes = need;
-        }
+        if ((rc = env->mem.grow(m * (28 * 4 + 8 + 4), env->tmp_bytes, {BG_BUF(env->d_tmp, 1)}))) return rc;
         int32_t *d_st = (int32_t *)env->d_tmp;
         int32_t *d_len = d_st + (size_t)m * 28;
         int8_t *d_seq = (int8_t *)(d_len + m);
@@ -1869,10 +1795,8 @@ int bgamd_env_run_sampled(bgamd_env *env, int flags, float temperature, int prec
     run.temperature = temperature;
     if (n_steps == 0) return BGAMD_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (!env->smp_words) {
-        HIPCHK(hipMalloc(&env->smp_words, (size_t)(env->v.n + 2) * 8));
-        HIPCHK(hipMalloc(&env->smp_score, (size_t)env->sv.cap_rows * 4));
-    }
+    if (!env->smp_words && (rc = env->mem.alloc_group({BG_BUF(env->smp_words, (size_t)(env->v.n + 2) * 8),
+                                                       BG_BUF(env->smp_score, (size_t)env->sv.cap_rows * 4)}))) return rc;
     HIPCHK(hipMemsetAsync(env->smp_words, 0, 2 * 8, s));            // the two counters: sums over the steps of this call
     env->sampled = true;
     env->smp_stream = s;
@@ -1984,20 +1908,22 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
     int rc;
     if (d_played) {
         an.ready = false;
-        if (!an.summary && (rc = an.allocate(n))) return rc;
+        AnaView &v = an.v;                             // all or none: summary != NULL says that every buffer is there
+        if (!an.summary && (rc = env->mem.alloc_group({BG_BUF(v.status, n * 4), BG_BUF(v.distinct, n * 4), BG_BUF(v.rank1, n * 4), BG_BUF(v.rank2, n * 4),
+                BG_BUF(v.v1_played, n * 4), BG_BUF(v.v1_best, n * 4), BG_BUF(v.v2_played, n * 4), BG_BUF(v.v2_best, n * 4), BG_BUF(v.error, n * 4),
+                BG_BUF(v.best, n * 32), BG_BUF(v.ppos, n * 4), BG_BUF(v.pslot, n * 4), BG_BUF(an.summary, ANA_SUMMARY * 8)}))) return rc;
     }
-    if (!se.cnt) {
-        uint32_t **per_game[] = {&se.cnt, &se.off, &se.fill, &se.kept, &se.koff, &se.skept, &se.soff};
-        for (uint32_t **p : per_game) HIPCHK(hipMalloc(p, (size_t)(n + 1) * 4));
-        HIPCHK(hipMalloc(&se.max, 8));
-        HIPCHK(hipMalloc(&se.d_info, 4 * 8));
-        HIPCHK(hipMalloc(&se.grp, (size_t)env->sv.cap_rows * 4));
-        HIPCHK(hipMalloc(&se.rank, (size_t)env->sv.cap_rows * 4));
+    if (!se.cnt) {                                     // all or none: cnt != NULL says that every buffer is there
+        const size_t per_game = (size_t)(n + 1) * 4, per_row = (size_t)env->sv.cap_rows * 4;
+        if ((rc = env->mem.alloc_group({BG_BUF(se.cnt, per_game), BG_BUF(se.off, per_game), BG_BUF(se.fill, per_game), BG_BUF(se.kept, per_game),
+                                        BG_BUF(se.koff, per_game), BG_BUF(se.skept, per_game), BG_BUF(se.soff, per_game),
+                                        BG_BUF(se.max, 8), BG_BUF(se.d_info, 4 * 8), BG_BUF(se.grp, per_row), BG_BUF(se.rank, per_row)})))
+            return rc;
     }
     auto grow_candidates = [&](long long need) {       // (at least 1 024 rows once there is one)
-        return grow_buffers(need > 0 && need < 1024 ? 1024 : need, se.c_cap,
-                            {{(void **)&se.c_rows, 32}, {(void **)&se.c_key, 4}, {(void **)&se.c_v1, 4}, {(void **)&se.c_v2, 4},
-                             {(void **)&se.c_rval, 4 * SRCH_ROLLS}, {(void **)&se.vmap, 4}});
+        return env->mem.grow(need > 0 && need < 1024 ? 1024 : need, se.c_cap,
+                             {BG_BUF(se.c_rows, 32), BG_BUF(se.c_key, 4), BG_BUF(se.c_v1, 4), BG_BUF(se.c_v2, 4),
+                              BG_BUF(se.c_rval, 4 * SRCH_ROLLS), BG_BUF(se.vmap, 4)});
     };
     // bound on the kept candidates (top_k = 0: read back below); the analysis keeps the played one beside the top_k
     long long n_cand = top_k > 0 && !margin ? n * (long long)(top_k + (d_played ? 1 : 0)) : 0;
@@ -2214,7 +2140,7 @@ int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_state
     hipStream_t s = (hipStream_t)stream;
     PrerollState &pre = env->pre;
     int rc;
-    if ((rc = grow_buffers(n, pre.cap, {{(void **)&pre.rows, 32}, {(void **)&pre.f, 4 * SRCH_ROLLS}}))) return rc;
+    if ((rc = env->mem.grow(n, pre.cap, {BG_BUF(pre.rows, 32), BG_BUF(pre.f, 4 * SRCH_ROLLS)}))) return rc;
 
     HIPCHK(hipMemsetAsync(&env->a_ctr[A_INTAKE], 0, 8, s));
     if ((rc = intake_positions(env, d_states28, d_turn, n, pre.rows, s))) return rc;
@@ -2269,17 +2195,19 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
     // the scratch env (exactly L lanes) and the buffers of this call
     if ((rc = scratch_env(env, &env->rscratch, L, true, 1, s))) return rc;
     bgamd_env *sc = env->rscratch;
-    if ((rc = grow_buffers(P, ro.cap_pos, {{(void **)&ro.pos, 32}})) ||
-        (rc = grow_buffers(n_fan, ro.cap_fan, {{(void **)&ro.fan, 32}, {(void **)&ro.fval, 4}})) ||
-        (rc = grow_buffers(N, ro.cap_trials, {{(void **)&ro.tval, 4}, {(void **)&ro.tturns, 4}})) ||
-        (rc = grow_buffers(L, ro.cap_lanes, {{(void **)&ro.lane, 4}, {(void **)&ro.trows, 32}, {(void **)&ro.tids, 4}, {(void **)&ro.tv, 4}})))
+    DevMem &mem = env->mem;
+    if ((rc = mem.grow(P, ro.cap_pos, {BG_BUF(ro.pos, 32)})) ||
+        (rc = mem.grow(n_fan, ro.cap_fan, {BG_BUF(ro.fan, 32), BG_BUF(ro.fval, 4)})) ||
+        (rc = mem.grow(N, ro.cap_trials, {BG_BUF(ro.tval, 4), BG_BUF(ro.tturns, 4)})) ||
+        (rc = mem.grow(L, ro.cap_lanes, {BG_BUF(ro.lane, 4), BG_BUF(ro.trows, 32), BG_BUF(ro.tids, 4), BG_BUF(ro.tv, 4)})))
         return rc;
-    if (vr && ((rc = grow_buffers(N, ro.cap_vtrials, {{(void **)&ro.tluck, 8}})) ||
-               (rc = grow_buffers(L, ro.cap_vlanes, {{(void **)&ro.vf, 4 * SRCH_ROLLS}})) ||
-               (rc = grow_buffers(P, ro.cap_vpos, {{(void **)&ro.f0, 4 * SRCH_ROLLS}, {(void **)&ro.m0, 8}}))))
+    if (vr && ((rc = mem.grow(N, ro.cap_vtrials, {BG_BUF(ro.tluck, 8)})) ||
+               (rc = mem.grow(L, ro.cap_vlanes, {BG_BUF(ro.vf, 4 * SRCH_ROLLS)})) ||
+               (rc = mem.grow(P, ro.cap_vpos, {BG_BUF(ro.f0, 4 * SRCH_ROLLS), BG_BUF(ro.m0, 8)}))))
         return rc;
-    if (d_group && (rc = grow_buffers(P, ro.cap_group, {{(void **)&ro.group, 4}}))) return rc;
-    if ((rc = ro.read_back_ready())) return rc;
+    if (d_group && (rc = mem.grow(P, ro.cap_group, {BG_BUF(ro.group, 4)}))) return rc;
+    if (!ro.host && (rc = mem.alloc_pinned(BG_BUF(ro.host, 8 * 8)))) return rc;        // the pinned words and the two events: first use
+    for (hipEvent_t &e : ro.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     unsigned long long *h = ro.host, *ctr = env->a_ctr;
 
     // the positions as rows; a bad state is refused before anything is played
@@ -2836,6 +2764,7 @@ int bgamd_pack_rows(const int32_t *d_states28, const int32_t *d_turn, int64_t n,
 
 struct bgamd_td {
     int device = 0;
+    DevMem mem;                            // owns every device buffer of td_buffers that has been allocated
     long long max_games = 0;
     TdView v{};
     bool has_weights = false, begun = false;
@@ -2875,17 +2804,17 @@ hipError_t td_read(bgamd_td *td, void *dst, const void *src, size_t bytes)
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, td->last_stream);
     return e != hipSuccess ? e : hipStreamSynchronize(td->last_stream);
 }
-// The learner's device buffers, the ONE list of them: bgamd_td_create allocates those of TD_AT_CREATE, the delayed replay and
-// bgamd_td_comm_init theirs at first use, bgamd_td_destroy frees whatever of the list is allocated.  A new buffer needs its member
-// AND its line here: one left out is never allocated and stays null, which its first kernel trips over at once.
+// The learner's device buffers, the ONE table of what to allocate and when: bgamd_td_create allocates those of TD_AT_CREATE, the delayed
+// replay and bgamd_td_comm_init theirs at first use -- through td->mem, which bgamd_td_destroy releases.  A new buffer is its member and
+// its line here: one left out is never allocated and stays null, which its first kernel trips over at once.
 enum TdWhen { TD_AT_CREATE, TD_AT_DELAY, TD_AT_COMM };
-struct TdBuf { void **ptr; size_t bytes; const char *name; TdWhen when; };
+struct TdBuf { DevBuf buf; TdWhen when; };
 std::vector<TdBuf> td_buffers(bgamd_td *td)
 {
     TdView &v = td->v;
     const size_t n = (size_t)td->max_games;
     const size_t partial_bytes = ((size_t)TD_MAX_GROUPS * TD_LD + 64) * 4;     // + a zeroed line: the dummy source of the pipelined trace pass
-#define TDBUF(ptr, bytes, when) TdBuf{(void **)&(ptr), (size_t)(bytes), #ptr, when}
+#define TDBUF(ptr, bytes, when) TdBuf{BG_BUF(ptr, bytes), when}
     return {
         TDBUF(v.theta, TD_LD * 4, TD_AT_CREATE),                  TDBUF(v.w1t, N_IN * N_HID * 4, TD_AT_CREATE),
         TDBUF(v.e, n * TD_LD * 4, TD_AT_CREATE),                  TDBUF(v.fac, n * TD_FLD * 4, TD_AT_CREATE),
@@ -2908,11 +2837,8 @@ std::vector<TdBuf> td_buffers(bgamd_td *td)
 // allocate the buffers of `when` that are not there yet; the error text names the one that failed
 int td_alloc(bgamd_td *td, TdWhen when)
 {
-    for (const TdBuf &b : td_buffers(td)) {
-        if (b.when != when || *b.ptr) continue;
-        const hipError_t e = hipMalloc(b.ptr, b.bytes);
-        if (e != hipSuccess) { g_hip_err = std::string("hipMalloc(") + b.name + "): " + hipGetErrorString(e); return BGAMD_E_HIP; }
-    }
+    for (const TdBuf &b : td_buffers(td))
+        if (b.when == when && !*b.buf.ptr) if (const int rc = td->mem.alloc(b.buf)) return rc;
     return BGAMD_OK;
 }
 // Σ over the slots of one of their 32-bit counters (nupd, act_cols, wr_cols)
@@ -2984,7 +2910,7 @@ int bgamd_td_destroy(bgamd_td *td)
     hipDeviceSynchronize();
     for (hipEvent_t e : td->ev) hipEventDestroy(e);
     bgamd_td_comm_destroy(td);
-    for (const TdBuf &b : td_buffers(td)) if (*b.ptr) hipFree(*b.ptr);
+    td->mem.release_all();
     delete td;
     return BGAMD_OK;
 }

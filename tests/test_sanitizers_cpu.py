@@ -67,3 +67,12 @@ def test_learner_step_plan_under_asan_ubsan(tmp_path):
     for lam in ("0", "0.25", "0.699999988", "1", "1.5"):
         for lazy in ({}, {"BGAMD_TD_LAZY": "0"}):
             assert len(P.run(exe, ["scale", lam, 400], lazy, extra_env=SAN_ENV)) == 400
+
+
+def test_device_memory_owner_under_asan_ubsan(tmp_path):
+    """The owner of a handle's device memory (csrc/bg_devmem.h, plain C++) compiled with the sanitizers into
+    tests/sanitize/devmem_driver.cpp and run over every failure point of tests/test_devmem_cpu.py's sequences.  A leak is a block the
+    fake backend still counts as live after release_all, not LeakSanitizer's business."""
+    import test_devmem_cpu as D
+    exe = D.build_driver(tmp_path / "devmem_driver", ("-fsanitize=address,undefined", "-fno-omit-frame-pointer"))
+    assert D.run(exe, SAN_ENV) == ["OK", str(D.CASES)]

@@ -67,3 +67,22 @@ def test_round5_evidence_is_consistent():
     assert 0.3 < step < 0.7
     g = json.load(open(os.path.join(ROOT, "profiles", "r05_v62_bench_2ranks_gloo.json")))
     assert g["n_gpus"] == 2 and g["ranks_seen"] == 2 and g["launched_by"] == "bench.py launch_ranks" and g["training_round"]["replicas_identical"]
+
+
+def test_codeobj_diff_of_the_library_with_itself():
+    """tools/codeobj_diff.py: the built library's gfx950 code object against itself is identical, section by section and symbol by symbol."""
+    import pytest
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import codeobj_diff
+    finally:
+        sys.path.pop(0)
+    lib = os.path.join(ROOT, "backgammon-engine_amd", "libbgamd.so")
+    if any(codeobj_diff.find_tool(t) is None for t in codeobj_diff.TOOLS):
+        pytest.skip("llvm-objcopy / clang-offload-bundler not installed")
+    assert os.path.exists(lib), "libbgamd.so is not built"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "codeobj_diff.py"), lib, lib], capture_output=True, text=True, cwd=ROOT)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0 and lines[-1] == "identical", r.stdout + r.stderr
+    assert [x.split()[:2] for x in lines[:3]] == [[".text", "identical:"], [".rodata", "identical:"], [".note", "identical:"]]
+    assert "function symbols" in lines[3] and "all at the same address and size" in lines[3]
