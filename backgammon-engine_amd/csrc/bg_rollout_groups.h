@@ -1,6 +1,6 @@
 // bg_rollout_groups.h -- kernels of the grouped rollout (bgamd_env_rollout_grouped, bgamd_env_rollout_paired_read, include/bgamd.h).
-// Included by bgamd.hip inside an anonymous namespace at the END of the file, after every other kernel: both are templates first
-// launched there, so that no other kernel of the code object moves.
+// Included by bgamd.hip inside an anonymous namespace just ahead of its KERNEL_ORDER list: both are templates whose entries stand
+// at that list's end, so that no other kernel of the code object moves.
 //
 //   intake    ro_group_intake (thread per position) : the caller's group table into the env's copy; a negative group, or one whose
 //             last trial's id (group + 1) T - 1 would not fit below 2^31, sets ERRF_RO_GROUP in the intake word

@@ -1,8 +1,8 @@
 // bg_sample.h -- the temperature-sampled step (bgamd_env_step_sampled, include/bgamd.h): two small passes over the rows the value net
 // has just evaluated, between the value net and the apply / boundary launch of a greedy step.  Included by bgamd.hip inside an anonymous
-// namespace at the END of the file, and both kernels are TEMPLATES (on their workgroup size) launched from there: a plain kernel's code
+// namespace just ahead of its KERNEL_ORDER list, and both kernels are TEMPLATES (on their workgroup size): a plain kernel's code
 // is emitted ahead of every kernel template's, where it would move boundary_kernel and the learner's kernels to other addresses (that
-// alone cost the greedy step 0.5 %); a template's code is emitted where it is first launched, here behind all the others.
+// alone cost the greedy step 0.5 %); a template's code is emitted where that list names it, behind the earlier ones.
 //
 //   pass A  sample_score_kernel : per row  s = d / T + g  (d = mover-side value - the lane's best, g = Gumbel noise of the row's planes),
 //                                 kept in score[row]; 64-bit atomicMax of (ordered score bits, ~key) into pick[lane], the maximum first

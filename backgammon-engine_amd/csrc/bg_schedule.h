@@ -1,5 +1,5 @@
 // bg_schedule.h -- host-only part of the streamed TD(lambda) replay: dealing a round's games to the replay slots.
-// Plain C++ (no HIP): bgamd.hip wraps it as bgamd_td_stream_schedule, tests/test_sanitizers_cpu.py compiles it under
+// Plain C++ (no HIP): bg_learner_host.h wraps it as bgamd_td_stream_schedule, tests/test_sanitizers_cpu.py compiles it under
 // AddressSanitizer + UBSan.  The reference applies a round's games one after another
 // (pysrc/TD(lambda) model/train.py:536-547); k slots replay them k at a time.
 #pragma once

@@ -1,6 +1,6 @@
 // bg_search_log.h -- the search log's pass (bgamd_env_set_search_log, include/bgamd.h): what a 2-ply search step of either kind decided,
 // turn by turn, as (pre-move row, played afterstate, V2 of the played candidate, its v1).  Included by bgamd.hip inside an anonymous
-// namespace at the end of the file, behind every other kernel.
+// namespace just ahead of its KERNEL_ORDER list, which places the kernel behind the earlier ones.
 //
 //   srch_log (lane per game) : between stage D's reduce (sv.best[g] holds the winner, c_v2 every kept candidate's V2) and apply_kernel,
 //                              which moves the lane -- so the lane's meta / ply and sv.root_rows are still those of the step's start

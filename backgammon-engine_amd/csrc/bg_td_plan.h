@@ -1,5 +1,5 @@
 // bg_td_plan.h -- host-only part of the TD(lambda) learner's step: which kernels a step of a given size runs, with which grids, and
-// the scale of the lazily scaled traces.  Plain C++ (no HIP), like bg_schedule.h: bgamd.hip issues the launches a TdPlan names,
+// the scale of the lazily scaled traces.  Plain C++ (no HIP), like bg_schedule.h: bg_learner_host.h issues the launches a TdPlan names,
 // tests/test_td_plan_cpu.py holds it against an independent restatement without a GPU, tests/test_sanitizers_cpu.py runs it under
 // AddressSanitizer + UBSan (tests/sanitize/td_plan_driver.cpp).  The kernels themselves: bg_learner.h, bg_fit.h, bg_eval.h.
 //

@@ -2,7 +2,7 @@
 
 Transcribed from the host code of commit 3f1f4b1 ("Fit the value net to rollout targets: a supervised learner step"), the parent of
 the change that introduced bg_td_plan.h -- from bgamd_td_create (the getenv lines), bgamd_td_step (the if / else-if chain of its
-launches), td_fuse_g_for, td_replay_delayed / bgamd_td_replay (the delayed route) in csrc/bgamd.hip as they stood there -- and NOT from
+launches), td_fuse_g_for, td_replay_delayed / bgamd_td_replay (the delayed route) in csrc/bgamd.hip as they stood there (that host code is csrc/bg_learner_host.h now) -- and NOT from
 the new header: it follows that function's order of statements, one Python line per C line, so that the two are two derivations."""
 import re
 

@@ -128,7 +128,7 @@ def test_lazy_scale_folds_back_twice_at_a_quarter():
     """learner_ref.scale_passes restates bgamd_td_step's scale bookkeeping (td_scale_step of csrc/bg_td_plan.h); the source line it mirrors is checked to be there (the device
     side of the claim: test_lambda_edges of tests/test_gpu_learner_steps.py)."""
     csrc = os.path.join(os.path.dirname(__file__), "..", "backgammon-engine_amd", "csrc")
-    src = open(os.path.join(csrc, "bgamd.hip")).read()
+    src = open(os.path.join(csrc, "bg_learner_host.h")).read()
     step = src[src.index("int bgamd_td_step("):src.index("int bgamd_td_apply(")]
     assert "td_scale_step(t, lambda, td->tune.lazy, td->scale)" in step           # the bookkeeping itself: bg_td_plan.h, for both replays
     plan = open(os.path.join(csrc, "bg_td_plan.h")).read()
