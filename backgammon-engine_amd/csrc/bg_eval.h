@@ -14,6 +14,7 @@
 #pragma once
 #include "bg_board.h"
 #include "bg_td_plan.h"                  // ROOT3_THREADS: the learner's step plan sizes the trajectory pass's grid by it
+#include "bg_step_plan.h"                // EVAL_THREADS, DELTA_THREADS, and the workgroup sizes of the root passes and of bg_eval_dense16.h: the env's step plan sizes their grids
 
 namespace bg {
 
@@ -21,7 +22,6 @@ constexpr int N_IN = 198, N_HID = 128;
 constexpr int N_PARAMS = N_HID * N_IN + N_HID + N_HID + 1;
 constexpr int K_STEPS = N_IN / 2;                  // 99
 constexpr int EVAL_LDS_BYTES = K_STEPS * 64 * 16;  // 101 376
-constexpr int EVAL_THREADS = 768;                  // 12 waves per CU (3 per SIMD): block-sparse tiles leave the MFMA pipe ~50 % busy, more waves fill it
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -286,11 +286,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_rows_f32_kernel(
 // in fp32 FMAs; hidden sigmoid, W2 dot, output sigmoid and the per-game arg-max are as in the dense kernel.
 // Lane = row, 32 hidden units at a time in registers, W1^T in LDS (132-float row stride), each lane's (row, Δ) list in LDS.
 // The sum is the same real number as the dense chain with a different association: values agree to ~1e-7.
-#ifndef BG_DELTA_THREADS
-#define BG_DELTA_THREADS 1024
-#endif
-constexpr int DELTA_THREADS = BG_DELTA_THREADS;         // 16 waves per CU, one workgroup per CU (LDS: W1^T + the lists).  -DBG_DELTA_THREADS=512/768: the round-5
-                                                        // co-residency experiment (2 / 3 waves per SIMD at 128 VGPRs: room for another kernel's workgroup on the CU)
+// DELTA_THREADS threads per workgroup (bg_step_plan.h, -DBG_DELTA_THREADS)
 #ifndef BG_DW_STRIDE
 #define BG_DW_STRIDE 132
 #endif

@@ -26,10 +26,7 @@
 
 namespace bg {
 
-constexpr int D16_THREADS = 256;                        // 4 waves: one per 32-unit column tile
-#ifndef BG_D16_WAVES
-#define BG_D16_WAVES 3                                   // waves per SIMD the register allocation aims at (= workgroups per CU)
-#endif
+// D16_THREADS = 256 (4 waves: one per 32-unit column tile) and BG_D16_WAVES = 3 (waves per SIMD the register allocation aims at): bg_step_plan.h
 constexpr int D16_LDS_BYTES = 2 * D16_XBUF_U4 * 16 + 2 * 4 * 32 * 4 + 2 * EVAL16_LUT_BYTES + N_HID * 4 + 3 * 1024;     // 26 624 + 1 024 + 256 + 512 + 3 072 (three tiles of rows)
 
 // Wl[part][s][c][l][j] = f16 part of  -log2(e) · W1[32c + (l&31)][feature(s, l>>5, j)];  tail step (s = 12): the h = 0 lanes

@@ -78,7 +78,7 @@ inline int relayout_w1_f16x2_root(const float *w1, uint16_t *wl)
 // lo inside a step: the same bits), organised like eval_rows_d16_kernel (bg_eval_dense16.h): a workgroup of four waves, wave c keeps the three
 // planes of ITS 32 hidden units in 156 registers for the whole launch, the 13 A operands of a 32-game tile are decoded once
 // into LDS (a quarter of the K-steps per wave), rows arrive by LDS-DMA two tiles ahead, one block barrier per tile.
-constexpr int ROOTR_THREADS = 256;
+// (ROOTR_THREADS = 256 threads: bg_step_plan.h)
 constexpr int ROOTR_LDS_BYTES = 2 * D16_XBUF_U4 * 16 + EVAL16_LUT_BYTES + 3 * 1024;
 
 __global__ __launch_bounds__(ROOTR_THREADS, 2) void root_hidden_resident_kernel(
@@ -175,14 +175,10 @@ __global__ __launch_bounds__(ROOTR_THREADS, 2) void root_hidden_resident_kernel(
 // hand: it goes on with THEIR root pass -- 8 tiles of 32 games, wave c = hidden units 32 c .. 32 c + 31, the same operands, the same MFMA
 // sequence per accumulator (K-step ascending; planes hi, mid, lo inside a step) and the same epilogue as root_hidden_resident_kernel:
 // the same bits.  Rows come from LDS (the roots half of the launch puts them there), no launch, no event, no round trip.
-constexpr int BROOT_THREADS = 256;                           // = LANE_NT of the boundary launch: four waves
-// games per workgroup of the boundary launch when it carries the root pass: 128 -- half the threads idle through the lane-per-game halves, 4 tiles per
+// BROOT_THREADS = 256 = LANE_NT of the boundary launch: four waves (bg_step_plan.h, as BROOT_GPW).
+// Games per workgroup of the boundary launch when it carries the root pass: 128 -- half the threads idle through the lane-per-game halves, 4 tiles per
 // workgroup, two workgroups per CU at 65 536 lanes and one on EVERY CU at 32 768 (-DBG_BROOT_GPW=256: a game per thread, 8 tiles; same-box A/B:
 // 65 536 lanes 0.1432 vs 0.1429 ms per step, 32 768 lanes 0.0945 vs 0.0994)
-#ifndef BG_BROOT_GPW
-#define BG_BROOT_GPW 128
-#endif
-constexpr int BROOT_GPW = BG_BROOT_GPW;
 constexpr int BROOT_TILES = BROOT_GPW / 32;
 // all 8 tiles' A operands are staged at once (one block barrier, then 8 x 39 MFMAs per wave back to back): a first version that staged
 // tile by tile behind a barrier each -- root_hidden_resident_kernel's loop -- cost the launch 16.7 us (a chain of 8 x (LDS round trip,

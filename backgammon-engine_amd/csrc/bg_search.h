@@ -12,7 +12,7 @@
 #pragma once
 
 constexpr int SRCH_ROLLS = 21;
-constexpr int SRCH_NT = 256;
+// (SRCH_NT = 256 threads per workgroup: bg_step_plan.h)
 
 // the 21 unordered rolls in the fixed order (1,1), (1,2), ..., (1,6), (2,2), ..., (6,6)
 __device__ __forceinline__ void srch_roll(int r, int &a, int &b)

@@ -15,6 +15,7 @@
 // (identical row, identical value) cannot change the result.
 #pragma once
 #include "bg_board.h"
+#include "bg_step_plan.h"                // LIST_SHARDS, N_ARENAS, and the workgroup sizes of bg_staged_kernels.h: shared with the host's step plan
 
 namespace bg {
 
@@ -144,10 +145,8 @@ struct StagedView {
 #endif
 enum { T_D1 = 0, T_D2 = BG_CTR_STRIDE, T_F = 2 * BG_CTR_STRIDE, T_U = 3 * BG_CTR_STRIDE, T_F2 = 4 * BG_CTR_STRIDE, T_UB = 5 * BG_CTR_STRIDE /* arenas 1, 2, 3 */,
        T_FS = 8 * BG_CTR_STRIDE /* F lists 1, 2, 3 */, T_DS = 11 * BG_CTR_STRIDE /* D1 lists 1, 2, 3 */, T_COUNT = 14 * BG_CTR_STRIDE };
-constexpr int LIST_SHARDS = 4;
 __host__ __device__ __forceinline__ int f_counter(int k) { return k == 0 ? T_F : T_FS + (k - 1) * BG_CTR_STRIDE; }
 __host__ __device__ __forceinline__ int d1_counter(int k) { return k == 0 ? T_D1 : T_DS + (k - 1) * BG_CTR_STRIDE; }
-constexpr int N_ARENAS = 4;
 __host__ __device__ __forceinline__ int arena_counter(int k) { return k == 0 ? T_U : T_UB + (k - 1) * BG_CTR_STRIDE; }
 
 }  // namespace bg

@@ -43,12 +43,7 @@ __device__ __forceinline__ void flag_overflow(const EnvView &e)
 }
 
 // ---- ply 1: lane per game -----------------------------------------------------------------------
-// lane-per-game kernels of the step boundary: threads per workgroup (measured 64 .. 1 024: 256 and 512 tie, smaller is
-// slower -- every workgroup pays two allocation atomics in the roots)
-#ifndef BG_LANE_NT
-#define BG_LANE_NT 256
-#endif
-constexpr int LANE_NT = BG_LANE_NT;
+// lane-per-game kernels of the step boundary: LANE_NT threads per workgroup (bg_step_plan.h, -DBG_LANE_NT)
 
 // The roots of a step in two halves (round 5): roots_issue does everything that needs no list position -- the roll, the ply-1 moves, the scan, the
 // lane's root row, turn log and dice -- and ISSUES the workgroup's two list allocations (returning atomics, thread 0); roots_collect waits for
@@ -181,15 +176,8 @@ __global__ __launch_bounds__(LANE_NT) void roots_kernel(EnvView e, StagedView sv
 // table the node threads filled, rebuilds the position and writes it to its final place (lane q -> row base + q: coalesced,
 // and the rows leave in reference order of the nodes).
 enum { MODE_PLY2 = 1, MODE_PLY3 = 2, MODE_LEAF = 3 };
-// threads per workgroup: every block iteration costs one same-address allocation atomic, so the leaf stage (2 000
-// block iterations of 256) takes big workgroups; the doubles plies are small and latency-bound and take smaller ones
-#ifndef BG_EXPAND_NT_PLY
-#define BG_EXPAND_NT_PLY 512
-#endif
-#ifndef BG_EXPAND_NT_LEAF
-#define BG_EXPAND_NT_LEAF 1024
-#endif
-__host__ __device__ constexpr int expand_threads(int mode) { return mode == 3 ? BG_EXPAND_NT_LEAF : BG_EXPAND_NT_PLY; }
+// threads per workgroup: the two sizes of bg_step_plan.h (-DBG_EXPAND_NT_LEAF, -DBG_EXPAND_NT_PLY)
+__host__ __device__ constexpr int expand_threads(int mode) { return mode == 3 ? EXPAND_NT_LEAF : EXPAND_NT_PLY; }
 constexpr uint32_t KEY_MASK = 0x00FFFFFFu;    // pass | origins | len
 
 // a thread's node with its game's planes and meta word, loaded ahead of use
@@ -614,11 +602,7 @@ __global__ __launch_bounds__(expand_threads(MODE_PLY2)) void doubles_kernel(EnvV
 //                               after the other on the workgroup's own allocations (leaf parents in F2, rows in the common arena);
 //   workgroups [n_dbl, grid)    the leaf stage over F, which in this mode holds nothing but the roots' output.
 // No workgroup waits for another.  The rows are the same rows, in another order of the arena -- nothing depends on that order
-// (a row's value is a function of the row; the arg-max keeps the smallest key).
-#ifndef BG_XALL_NT
-#define BG_XALL_NT 512
-#endif
-constexpr int XALL_NT = BG_XALL_NT;
+// (a row's value is a function of the row; the arg-max keeps the smallest key).  XALL_NT threads per workgroup (bg_step_plan.h, -DBG_XALL_NT).
 __global__ __launch_bounds__(XALL_NT, 4) void expand_all_kernel(EnvView e, StagedView sv, unsigned n_dbl, unsigned dbl_npb, unsigned parts,
                                                                   unsigned long long *__restrict__ zero_words, int n_zero_words)
 {

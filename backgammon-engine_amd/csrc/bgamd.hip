@@ -9,6 +9,8 @@
 //   values   float[cap]     value-net output per row
 // Greedy step: roots -> stage<PLY2> -> stage<PLY3> -> stage<LEAF> (bg_staged_kernels.h) -> eval (bg_eval.h) -> apply.
 // Random step: rnd_tasks -> rnd_count -> rnd_select (bg_random_kernels.h).  emit_kernel serves the ordered enumerate API.
+// What a greedy step launches and how big -- the kernel variants, the grids, the row arenas, the BGAMD_* switches and their defaults --
+// is decided once per run by step_plan (bg_step_plan.h, plain C++, checked without a GPU); GreedyRun::step issues what the plan names.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -35,10 +37,14 @@
 #ifdef BGAMD_EXPERIMENTAL
 #include "bg_eval_mfma.h"
 #include "bg_eval_dense16.h"
+constexpr bool EXPERIMENTAL_BUILD = true;
+#else
+constexpr bool EXPERIMENTAL_BUILD = false;
 #endif
 #include "bg_learner.h"
 #include "bg_fit.h"
 #include "bg_schedule.h"
+#include "bg_step_plan.h"
 #include "bg_movegen.h"
 #include "bg_staged.h"
 
@@ -796,8 +802,7 @@ struct bgamd_env {
     StagedView sv{};
     RandomView rv{};
     NetTables net;                         // the value net's device tables (a scratch env: its parent's, see scratch_env)
-    bool mfma_delta = false;               // BGAMD_MFMA_DELTA=1: eval_rows_mdelta_kernel instead of eval_rows_delta_kernel
-    bool d16 = false;                      // BGAMD_F16X2_RESIDENT=1: eval_rows_d16_kernel (W1 resident in registers) for BGAMD_F16X2 -- measured 6 % slower than round 1's eval_rows_f16x2_kernel
+    StepTuning tune;                       // the switches of the greedy step's dispatch (bg_step_plan.h), read at create
     int n_cu = 256;
     hipStream_t side = nullptr;            // second stream: the root pass of the value net runs beside the doubles plies
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;   //   (fork after roots_kernel, join before the incremental kernel)
@@ -812,21 +817,6 @@ struct bgamd_env {
     void *d_tmp = nullptr;                 // ... and of its enumerate call (states | seq | len), grown on demand
     long long tmp_bytes = 0;
     int choice[4] = {0, 0, 0, 0};           // kernels of the last greedy step (bgamd_env_kernel_choice)
-    bool list_shards = true;               // the roots' node lists in LIST_SHARDS parts (BGAMD_LIST_SHARDS=0: one list each)
-    bool split_arena = true;               // the greedy step (incremental value net) keeps hit-free rows and the others in two arenas (BGAMD_SPLIT_ARENA=0: one)
-    bool expand_merged = true;             // doubles plies + leaf stage in one launch (expand_all_kernel); BGAMD_EXPAND_MERGED=0: two launches
-    int expand_parts = 3;                  // timing experiments (BGAMD_EXPAND_PARTS): 1 = only the doubles turns are expanded, 2 = only the others
-    int expand_dbl_npb = 128;              // ply-1 nodes a doubles workgroup takes per iteration (BGAMD_EXPAND_DBL_NPB: 64 .. 512)
-    int expand_dbl_pct = 0;                // share of that launch's workgroups that takes the doubles turns (BGAMD_EXPAND_DBL_PCT: 5 .. 95; 0 = by env
-                                           // size: GreedyRun::init), the others take the non-doubles leaf stage
-    bool root_in_boundary = true;          // inside a run the root pass of step t + 1 runs in the boundary launch of step t (bg_root_resident.h);
-                                           //   BGAMD_ROOT_IN_BOUNDARY=0: a launch of its own every step, as up to round 3
-    bool overlap = true;                   // BGAMD_NO_OVERLAP=1: everything on the caller's stream; BGAMD_OVERLAP=1: second stream for small envs too
-    bool root_f32_mfma = false;            // root term by the f32 MFMA chain instead of the bf16 x 3 split (BGAMD_ROOT_F32=1)
-    bool root_resident = true;             // the bf16 x 3 root pass with W1 resident in registers (same bits as the LDS-staged kernel, BGAMD_ROOT_RESIDENT=0).
-                                           //   The leaf stage starts less obstructed beside it: with the counters packed (rounds 2-3a) the value net paid that
-                                           //   back (step 0.1501 vs 0.1504 ms); with every counter on its own line it does not (leaf stage 0.0302 -> 0.0260,
-                                           //   doubles plies 0.0180 -> 0.0195, step 0.1458 -> 0.1445 ms, same box, three interleaved runs)
     // kernel timing
     unsigned timing = 0;                   // bit k: bracket kernel group k with HIP events
     unsigned timing_stride = 1;            // ... on every timing_stride-th launch of the group (an event pair costs ~4 us)
@@ -1008,45 +998,7 @@ static int env_create(bgamd_env **out, int64_t n_games, int device, uint64_t see
     int rc = env_allocate(env, n_games, seed, lane_offset, lane_stride, arena_rows, borrows_weights);
     if (rc == BGAMD_OK) rc = bgamd_env_reset(env, nullptr);
     if (rc != BGAMD_OK) return fail(rc, g_hip_err);
-#ifdef BGAMD_EXPERIMENTAL
-    // every BGAMD_* switch reads the same way: set and atoi() != 0 (bench.py mirrors it through bgamd_env_kernel_choice, not the environment)
-    auto on = [](const char *name) { const char *v = getenv(name); return v != nullptr && atoi(v) != 0; };
-    auto off = [](const char *name) { const char *v = getenv(name); return v != nullptr && atoi(v) == 0; };
-    env->root_f32_mfma = on("BGAMD_ROOT_F32");
-    env->root_resident = !off("BGAMD_ROOT_RESIDENT");
-    // round 3's K-compacted MFMA delta kernel (bg_eval_mfma.h) is correct and canonical but measured 10 % slower than the VALU
-    // kernel on the same box (NOTEBOOK.md): opt-in, experimental build only
-    env->mfma_delta = on("BGAMD_MFMA_DELTA");
-    env->d16 = on("BGAMD_F16X2_RESIDENT");
-#endif
-    // Where the root pass runs (round 4, profiles/r04_lanes_32768_anatomy.txt, r04_ab_root_pass_in_boundary.txt): inside the boundary launch from 24 576 lanes
-    // -- there a boundary workgroup owns 128 games (BROOT_GPW), so 32 768 lanes still put a workgroup on every CU: 94.5 vs 98.7 us per step with the pass as a
-    // launch of its own (65 536: 143.2 vs 143.6; 16 384: 72.0 vs 71.7, a tie: smaller envs keep the launch) -- and always on the caller's stream.
-    env->root_in_boundary = n_games >= 24576 && LANE_NT == BROOT_THREADS;
-    env->overlap = false;
-#ifdef BGAMD_EXPERIMENTAL
-    // Round 5: the launch structures that lost their A/B (rounds 1-4) are honoured by the EXPERIMENTAL build only, as bit-identity references
-    // (tests/test_gpu_experimental.py): the root pass forced in / out of the boundary launch (BGAMD_ROOT_IN_BOUNDARY) or forked onto the env's second
-    // stream (BGAMD_OVERLAP), the expansion as two launches (BGAMD_EXPAND_MERGED=0), one row arena (BGAMD_SPLIT_ARENA=0), unsharded node lists
-    // (BGAMD_LIST_SHARDS=0), and the expansion launch's timing knobs.  The default build reads none of them.
-    {
-        const char *rib = getenv("BGAMD_ROOT_IN_BOUNDARY");
-        if (rib) env->root_in_boundary = atoi(rib) != 0 && LANE_NT == BROOT_THREADS;
-        const char *xm = getenv("BGAMD_EXPAND_MERGED");
-        env->expand_merged = xm ? atoi(xm) != 0 : true;
-        const char *xp = getenv("BGAMD_EXPAND_DBL_PCT");
-        if (xp && atoi(xp) >= 5 && atoi(xp) <= 95) env->expand_dbl_pct = atoi(xp);
-        const char *ls = getenv("BGAMD_LIST_SHARDS");
-        env->list_shards = ls ? atoi(ls) != 0 : true;
-        const char *sa = getenv("BGAMD_SPLIT_ARENA");
-        env->split_arena = sa ? atoi(sa) != 0 : true;
-        const char *xq = getenv("BGAMD_EXPAND_PARTS");
-        if (xq && atoi(xq) >= 1 && atoi(xq) <= 3) env->expand_parts = atoi(xq);
-        const char *xn = getenv("BGAMD_EXPAND_DBL_NPB");
-        if (xn && atoi(xn) >= 64 && atoi(xn) <= XALL_NT) env->expand_dbl_npb = atoi(xn) & ~63;
-    }
-    env->overlap = getenv("BGAMD_NO_OVERLAP") == nullptr && getenv("BGAMD_OVERLAP") != nullptr && atoi(getenv("BGAMD_OVERLAP")) != 0;
-#endif
+    env->tune = step_tuning_from_env(getenv, EXPERIMENTAL_BUILD, n_games);
     if (hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&env->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&env->ev_join, hipEventDisableTiming) != hipSuccess)
@@ -1395,9 +1347,7 @@ int bgamd_env_step_random(bgamd_env *env, int flags, const uint32_t *d_choice_u3
     {
         KTimer t(env, s, 3);
         hipLaunchKernelGGL(rnd_tasks_kernel, grid1(n, 256), dim3(256), 0, s, env->v, env->rv, flags, -1.0f);
-        long long b = (n * 64 + 255) / 256;
-        const long long lim = (long long)env->n_cu * 8;
-        hipLaunchKernelGGL(rnd_count_kernel, dim3((unsigned)(b > lim ? lim : b)), dim3(256), 0, s, env->v, env->rv);
+        hipLaunchKernelGGL(rnd_count_kernel, dim3((unsigned)rnd_count_grid(n * 64, env->n_cu)), dim3(256), 0, s, env->v, env->rv);
         hipLaunchKernelGGL(rnd_select_kernel, grid1(n, 256), dim3(256), 0, s, env->v, env->rv, flags, d_choice_u32);
     }
     HIPCHK(hipGetLastError());
@@ -1471,7 +1421,9 @@ int bgamd_env_load_weights_slot(bgamd_env *env, int slot, const float *h_weights
     return BGAMD_OK;
 }
 
-static int launch_eval(bgamd_env *env, int slot, int precision, const unsigned long long *n_rows_ptr, long long n_rows_imm,
+// The dense evaluators over n_rows_imm rows, or over *n_rows_ptr (<= n_rows_imm) of them.  g: eval_grids of the rows expected -- of
+// n_rows_imm, or, when the count is on the device, of a greedy step's worth of the env's lanes (StepPlan::eval)
+static int launch_eval(bgamd_env *env, int slot, int precision, const EvalGrids &g, const unsigned long long *n_rows_ptr, long long n_rows_imm,
                        const uint4 *rows, float *values, const uint2 *info, unsigned long long *best, hipStream_t s)
 {
     if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
@@ -1480,21 +1432,13 @@ static int launch_eval(bgamd_env *env, int slot, int precision, const unsigned l
     const NetTables &t = env->net;
     const float *b1 = t.b1(slot), *w2 = t.w2(slot), *b2 = t.b2(slot);
     unsigned long long *rows_ctr = n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : nullptr, *ksteps = n_rows_ptr ? &env->v.counters[C_KSTEPS] : nullptr;
-    // every workgroup first stages W1 in LDS: no more workgroups than the rows can use (a greedy step averages ~18
-    // rows per game; more than the estimate only means more tiles per wave)
-    const long long est_rows = n_rows_ptr ? env->v.n * 24 : n_rows_imm;
-    long long eb = (est_rows + (EVAL_THREADS / 64) * 32 - 1) / ((EVAL_THREADS / 64) * 32);
-    eb = eb < 1 ? 1 : (eb > env->n_cu ? env->n_cu : eb);
-    const dim3 egrid((unsigned)eb);
+    const dim3 egrid((unsigned)g.lds);
     KTimer timer(env, s, 1);
 #ifdef BGAMD_EXPERIMENTAL
-    if (precision == BGAMD_F16X2 && env->d16) {
-        long long tiles = (est_rows + 31) / 32;
-        const long long per_cu = BG_D16_WAVES;                                                     // 4-wave workgroups per CU
-        long long wg = tiles < 1 ? 1 : (tiles > per_cu * env->n_cu ? per_cu * env->n_cu : tiles);
-        hipLaunchKernelGGL(eval_rows_d16_kernel<2>, dim3((unsigned)wg), dim3(D16_THREADS), D16_LDS_BYTES, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
+    if (precision == BGAMD_F16X2 && env->tune.d16)
+        hipLaunchKernelGGL(eval_rows_d16_kernel<2>, dim3((unsigned)g.d16), dim3(D16_THREADS), D16_LDS_BYTES, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
                            (const uint4 *)t.d_wd16[slot], (const uint2 *)t.d_lut16, w2, b2, values, info, best, ksteps, (unsigned long long *)nullptr, 0);
-    } else
+    else
 #endif
     if (precision == BGAMD_F16X2)
         hipLaunchKernelGGL(eval_rows_f16x2_kernel, egrid, dim3(EVAL_THREADS), EVAL16X2_LDS_TOTAL, s, rows, n_rows_ptr, n_rows_imm, rows_ctr,
@@ -1509,48 +1453,61 @@ static int launch_eval(bgamd_env *env, int slot, int precision, const unsigned l
     return BGAMD_OK;
 }
 
-// The incremental value net's root pass: hidden[n][N_HID] = W1 x + b1 of the n root rows (one dense product per GAME).  f32_chain: the
-// caller honours BGAMD_ROOT_F32 (experimental build)
-static void launch_root_pass(bgamd_env *env, int slot, const uint4 *rows, long long n, float *hidden, [[maybe_unused]] bool f32_chain, hipStream_t s)
+// The incremental value net's root pass: hidden[n][N_HID] = W1 x + b1 of the n root rows, by the kernel `kind` names on `grid` workgroups
+// (root_pass_kind, root_pass_grid: bg_step_plan.h)
+static void launch_root_pass(bgamd_env *env, int slot, [[maybe_unused]] RootPass kind, long long grid, const uint4 *rows, long long n, float *hidden, hipStream_t s)
 {
     const NetTables &t = env->net;
 #ifdef BGAMD_EXPERIMENTAL
-    if (f32_chain && env->root_f32_mfma)
-        hipLaunchKernelGGL(eval_rows_f32_kernel<true>, dim3(env->n_cu), dim3(EVAL_THREADS), EVAL_LDS_TOTAL, s, rows,
+    if (kind == RootPass::F32_CHAIN)
+        hipLaunchKernelGGL(eval_rows_f32_kernel<true>, dim3((unsigned)grid), dim3(EVAL_THREADS), EVAL_LDS_TOTAL, s, rows,
                            (const unsigned long long *)nullptr, n, (unsigned long long *)nullptr, (const float4 *)t.d_wl[slot], t.b1(slot),
                            t.w2(slot), t.b2(slot), hidden, (const uint2 *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
-    else if (!env->root_resident) {
-        long long blocks = ((n + 31) / 32 + ROOT3_THREADS / 64 - 1) / (ROOT3_THREADS / 64);
-        if (blocks > env->n_cu) blocks = env->n_cu;
-        hipLaunchKernelGGL(root_hidden_bf16x3_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOT3_THREADS), ROOT3_LDS_TOTAL, s, rows, n,
+    else if (kind == RootPass::LDS_STAGED)
+        hipLaunchKernelGGL(root_hidden_bf16x3_kernel, dim3((unsigned)grid), dim3(ROOT3_THREADS), ROOT3_LDS_TOTAL, s, rows, n,
                            (const uint4 *)t.d_wl3[slot], (const uint2 *)t.d_lut, t.b1(slot), hidden);
-    } else
+    else
 #endif
-    {
-        long long blocks = (n + 31) / 32;
-        if (blocks > 2ll * env->n_cu) blocks = 2ll * env->n_cu;                 // two 4-wave workgroups per CU (256 VGPRs each wave)
-        hipLaunchKernelGGL(root_hidden_resident_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(ROOTR_THREADS), ROOTR_LDS_BYTES, s, rows, n,
-                           t.root_w(slot), t.root_lut(), t.b1(slot), hidden);
-    }
+    hipLaunchKernelGGL(root_hidden_resident_kernel, dim3((unsigned)grid), dim3(ROOTR_THREADS), ROOTR_LDS_BYTES, s, rows, n,
+                       t.root_w(slot), t.root_lut(), t.b1(slot), hidden);
+}
+
+// The incremental value net over the rows of sv on `grid` workgroups (delta_grid, bg_step_plan.h).  A greedy step: *n_rows_ptr rows, in
+// arenas of sv.b_base rows when that is set, and zero_words, the counter set to clear for the next roots (or NULL).  A caller with its
+// own rows: n_rows_ptr NULL, n_rows_imm rows from 0, no counters.  mfma: eval_rows_mdelta_kernel (experimental build; one arena).
+static void launch_delta(bgamd_env *env, int slot, [[maybe_unused]] bool mfma, long long grid, const StagedView &sv, const unsigned long long *n_rows_ptr,
+                         long long n_rows_imm, float *values, unsigned long long *zero_words, hipStream_t s)
+{
+    const NetTables &t = env->net;
+    unsigned long long *rows_ctr = n_rows_ptr ? &env->v.counters[C_ROWS_EVAL] : nullptr, *ksteps = n_rows_ptr ? &env->v.counters[C_KSTEPS] : nullptr;
+    const int n_zero = n_rows_ptr ? (int)T_COUNT : 0;
+#ifdef BGAMD_EXPERIMENTAL
+    if (mfma)
+        hipLaunchKernelGGL(eval_rows_mdelta_kernel, dim3((unsigned)grid), dim3(MD_THREADS), MD_LDS_TOTAL, s, (const uint4 *)sv.u_rows, n_rows_ptr, n_rows_imm,
+                           rows_ctr, (const uint4 *)t.d_wm[slot], t.w2(slot), t.b2(slot), (const uint4 *)sv.root_rows, (const float *)sv.root_hidden, values,
+                           (const uint2 *)sv.u_info, sv.best, ksteps, zero_words, n_zero, &env->v.counters[C_ERR], (unsigned long long)ERRF_DELTA);
+    else
+#endif
+    hipLaunchKernelGGL(eval_rows_delta_kernel, dim3((unsigned)grid), dim3(DELTA_THREADS), DELTA_LDS_TOTAL, s, (const uint4 *)sv.u_rows, n_rows_ptr, n_rows_imm,
+                       rows_ctr, (const float4 *)t.d_wt[slot], t.w2(slot), t.b2(slot), (const uint4 *)sv.root_rows, (const float *)sv.root_hidden, values,
+                       (const uint2 *)sv.u_info, sv.best, ksteps, zero_words, n_zero, &env->v.counters[C_ERR], (unsigned long long)ERRF_DELTA,
+                       sv.b_base > 0 ? (const unsigned long long *)&sv.tops[T_UB] : (const unsigned long long *)nullptr,
+                       (long long)sv.b_base);                     // (the counters of arenas 1, 2, 3 follow one another from T_UB)
 }
 
 }  // extern "C"
 
 // The sampled step's two passes (bg_sample.h) on s, between the value net and the apply
 static void launch_sample_passes(bgamd_env *env, const EnvView &ev, const unsigned long long *tops, long long b_base, float temperature,
-                                 int n_cu, hipStream_t s)
+                                 const StepPlan &p, hipStream_t s)
 {
     const long long n = ev.n, cap_rows = env->sv.cap_rows;
     const SampleView sm{env->smp_words + 2, env->smp_words, env->smp_score};
     hipMemsetAsync(sm.pick, 0, (size_t)n * 8, s);
-    // a greedy step averages ~18 rows per game: no more workgroups than the rows can use.  Pass A is arithmetic (three Philox blocks and two
-    // logarithms per row) and takes every wave slot; pass B is a compare per row and ends in one atomic per workgroup and counter
-    const long long want = (n * 24 + SRCH_NT - 1) / SRCH_NT;
-    const long long ga = want < (long long)n_cu * 8 ? want : (long long)n_cu * 8, gb = want < (long long)n_cu * 2 ? want : (long long)n_cu * 2;
-    hipLaunchKernelGGL(sample_score_kernel<SRCH_NT>, dim3((unsigned)(ga < 1 ? 1 : ga)), dim3(SRCH_NT), 0, s, ev, tops, b_base, cap_rows,
+    hipLaunchKernelGGL(sample_score_kernel<SRCH_NT>, dim3((unsigned)p.sample_score_grid), dim3(SRCH_NT), 0, s, ev, tops, b_base, cap_rows,
                        (const uint4 *)env->sv.u_rows, (const uint2 *)env->sv.u_info, (const float *)env->v.values,
                        (const unsigned long long *)env->sv.best, temperature, sm);
-    hipLaunchKernelGGL(sample_pick_kernel<SRCH_NT>, dim3((unsigned)(gb < 1 ? 1 : gb)), dim3(SRCH_NT), 0, s, n, tops, b_base, cap_rows,
+    hipLaunchKernelGGL(sample_pick_kernel<SRCH_NT>, dim3((unsigned)p.sample_pick_grid), dim3(SRCH_NT), 0, s, n, tops, b_base, cap_rows,
                        (const uint2 *)env->sv.u_info, (const float *)env->v.values, env->sv.best, sm);
 }
 
@@ -1562,7 +1519,6 @@ namespace {
 // their time scales with 1/CUs.  profiles/r02_cu_partition_group_run.txt)
 struct StepStreams {
     hipStream_t gen, root;
-    int n_cu;
 };
 
 // State of a run of greedy steps on one env (what bgamd_env_run_greedy kept in locals)
@@ -1571,14 +1527,12 @@ struct GreedyRun {
     int flags, slot, precision, parity = 0;
     float epsilon;
     float temperature = 0.0f;              // > 0: the sampled step (set after init() by bgamd_env_run_sampled, which passes epsilon 0)
-    bool incremental;
-    long long xall_nd = 1, xall_nl = 1;    // expand_all_kernel: workgroups for the doubles turns / for the non-doubles leaf stage
+    StepPlan plan;                         // what a step of this run launches, and how big (bg_step_plan.h)
     StagedView sv;
     EnvView ev;                            // the env's view as this run's launches take it (ring log: the slots of the step at hand)
     long long cur_step = 0;                // ring log: the env step being played
     bool root_ready = false;               // the boundary launch of the step before has already run this step's root pass
     bool first_of_run = true;              // no step since begin() (read by the BG_ABL_STEP timing ablation only)
-    const float *b1, *w2, *b2;
 
     int init(bgamd_env *e, int fl, float eps, int prec)
     {
@@ -1586,35 +1540,11 @@ struct GreedyRun {
         slot = (fl & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
         if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
         if (prec != BGAMD_F32 && prec != BGAMD_BF16 && prec != BGAMD_F16X2 && prec != BGAMD_F32_DENSE) return BGAMD_E_INVALID;
-        incremental = prec == BGAMD_F32;
-        b1 = env->net.b1(slot); w2 = env->net.w2(slot); b2 = env->net.b2(slot);
+        plan = step_plan(env->tune, env->v.n, env->n_cu, env->sv.cap_rows, prec, env->net.wm_ok[slot]);
         sv = env->sv;
         sv.tops = env->tops_base;
-        // two row arenas (by class) for the incremental value net; the other value-net kernels read one
-        sv.b_base = (incremental && env->split_arena) ? (env->sv.cap_rows / N_ARENAS) & ~63ll : 0;
-        {   // grid of expand_all_kernel: two 512-thread workgroups per CU are resident, the first xall_nd take the doubles turns (one of each kind
-            // per CU at the default share); the roots' lists in LIST_SHARDS parts when both counts divide
-#ifdef BG_XALL_WG_PER_CU                                                                     // (the round-5 co-residency experiment: fewer, so that one fits beside a value-net workgroup)
-            const long long n = env->v.n, slots = (long long)BG_XALL_WG_PER_CU * (long long)env->n_cu;
-#else
-            const long long n = env->v.n, slots = (1024 / XALL_NT) * (long long)env->n_cu;       // 16 waves of expand_all_kernel per CU
-#endif
-            long long nd = (n * 4 + 63) / 64;                       // doubles: ~64 ply-1 nodes per workgroup in a small env (a sixth of the lanes x <= 15)
-            // the share of workgroups for the doubles turns: BGAMD_EXPAND_DBL_PCT, else by env size -- the doubles chains are what the launch waits
-            // for, and the fewer lanes, the more so (32 768 lanes: 70 % 22.9 us, 50 % 25.1; 65 536: 62 % 28.5, 50 % 29.2; 16 384: 50 % 20.7, 63 % 21.3)
-            const int pct = env->expand_dbl_pct > 0 ? env->expand_dbl_pct : (n >= 49152 ? 62 : (n >= 24576 ? 70 : 50));
-            long long nd_lim = slots * pct / 100;
-            if (nd_lim >= LIST_SHARDS) nd_lim -= nd_lim % LIST_SHARDS;          // (both counts multiples of the list parts: a full launch keeps the lists in parts)
-            nd = nd < 1 ? 1 : (nd > nd_lim ? nd_lim : nd);
-            long long nl = (n * 16 + XALL_NT - 1) / XALL_NT;
-            const long long nl_lim = slots - nd_lim < 1 ? 1 : slots - nd_lim;
-            nl = nl < 1 ? 1 : (nl > nl_lim ? nl_lim : nl);
-            xall_nd = nd; xall_nl = nl;
-            sv.shards = (env->expand_merged && env->list_shards && nd % LIST_SHARDS == 0 && nl % LIST_SHARDS == 0) ? LIST_SHARDS : 1;
-        }
-#ifdef BGAMD_EXPERIMENTAL
-        if (env->mfma_delta && env->net.wm_ok[slot]) sv.b_base = 0;
-#endif
+        sv.b_base = plan.b_base;
+        sv.shards = plan.shards;
         parity = 0;
         root_ready = false;
         ev = env->v;
@@ -1633,15 +1563,6 @@ struct GreedyRun {
         cur_step = env->traj_step++;
         ev.log_slot = cur_step % ev.traj_ring;
     }
-    dim3 egrid(long long max_items, int mode, int n_cu) const    // expand_kernel: 48 B of LDS per thread, 2 048 threads per CU
-    {
-        const int nt = expand_threads(mode);
-        long long b = (max_items + nt - 1) / nt;
-        // one workgroup per CU for the 1 024-thread leaf stage (82 VGPRs: that is what fits; a second round of workgroups
-        // would start its latency chain from scratch, a second iteration of the same workgroup has its nodes prefetched)
-        const long long lim = (long long)n_cu * (nt >= 1024 ? 1 : 2048 / nt);
-        return dim3((unsigned)(b < 1 ? 1 : (b > lim ? lim : b)));
-    }
     // two sets of list counters: step t uses set t & 1.  Inside a run the apply of step t and the roots of step t+1
     // share one launch (boundary_kernel); the value-net kernel of step t clears the set those roots allocate from.
     int begin(hipStream_t s)
@@ -1659,17 +1580,17 @@ struct GreedyRun {
     {
         int rc;
         if ((rc = init(e, fl, 0.0f, BGAMD_F32)) || (rc = begin(s))) return rc;
-        return step(StepStreams{s, s, e->n_cu}, false, true);
+        return step(StepStreams{s, s}, false, true);
     }
     int step(const StepStreams &ss, bool more, bool score_only = false)
     {
         const long long n = env->v.n;
         hipStream_t s = ss.gen;
-        env->choice[0] = incremental ? ((env->mfma_delta && env->net.wm_ok[slot]) ? 1 : 0)
-                                     : (precision == BGAMD_F32_DENSE ? 2 : precision == BGAMD_F16X2 ? (env->d16 ? 4 : 3) : 5);
-        const bool own_root_launch = incremental && !root_ready;
-        env->choice[2] = ((own_root_launch && ss.root != s) ? 1 : 0) | (env->expand_merged ? 2 : 0);
-        env->choice[1] = !incremental ? 0 : (!own_root_launch ? 4 : (env->root_f32_mfma ? 3 : (env->root_resident ? 1 : 2)));      // 4: it ran inside the boundary launch before
+        const StepPlan &p = plan;
+        const bool own_root_launch = bg::own_root_launch(p, root_ready);
+        env->choice[0] = p.choice_eval;
+        env->choice[1] = step_choice_root(p, root_ready);
+        env->choice[2] = step_choice_forked(p, root_ready, ss.root != s) | (env->tune.expand_merged ? 2 : 0);
         if (own_root_launch) {
             // The value net's root pass (one dense W1 x + b1 per GAME) needs only the root rows the roots just wrote.
             // It runs on a second stream beside the doubles plies -- small latency-bound launches that leave
@@ -1684,21 +1605,21 @@ struct GreedyRun {
 #endif
             {
                 KTimer t(env, s2, 6);
-                launch_root_pass(env, slot, (const uint4 *)sv.root_rows, n, sv.root_hidden, true, s2);
+                launch_root_pass(env, slot, p.root, p.root_grid, (const uint4 *)sv.root_rows, n, sv.root_hidden, s2);
             }
             if (s2 != s) HIPCHK(hipEventRecord(env->ev_join, s2));
         }
         StagedView sv_next = sv;
         sv_next.tops = env->tops_base + (parity ^ 1) * T_COUNT;
 #ifdef BGAMD_EXPERIMENTAL
-        if (!env->expand_merged) {                             // rounds 1-4's two launches (bit-identity reference)
+        if (!env->tune.expand_merged) {                        // rounds 1-4's two launches (bit-identity reference)
             {
                 KTimer t(env, s, 4);
-                hipLaunchKernelGGL(doubles_kernel, egrid(n * 4, MODE_PLY2, ss.n_cu), dim3(expand_threads(MODE_PLY2)), 0, s, ev, sv);
+                hipLaunchKernelGGL(doubles_kernel, dim3((unsigned)p.ply2_grid), dim3(expand_threads(MODE_PLY2)), 0, s, ev, sv);
             }
             {
                 KTimer t(env, s, 5);
-                hipLaunchKernelGGL(expand_kernel<MODE_LEAF>, egrid(n * 16, MODE_LEAF, ss.n_cu), dim3(expand_threads(MODE_LEAF)), 0, s, ev, sv);
+                hipLaunchKernelGGL(expand_kernel<MODE_LEAF>, dim3((unsigned)p.leaf_grid), dim3(expand_threads(MODE_LEAF)), 0, s, ev, sv);
             }
         } else
 #endif
@@ -1706,65 +1627,39 @@ struct GreedyRun {
             // one launch: the doubles turns' plies 2, 3 and leaf stage on the first workgroups, the non-doubles leaf stage on the others
             // (two 512-thread workgroups per CU are resident: one of each kind per CU at the default share)
             KTimer t(env, s, 5);
-            const long long nd = xall_nd, grid = xall_nd + xall_nl;
-            hipLaunchKernelGGL(expand_all_kernel, dim3((unsigned)grid), dim3(XALL_NT), 0, s, ev, sv, (unsigned)nd,
-                               (unsigned)env->expand_dbl_npb, (unsigned)env->expand_parts, more ? sv_next.tops : (unsigned long long *)nullptr,
+            hipLaunchKernelGGL(expand_all_kernel, dim3((unsigned)(p.xall_nd + p.xall_nl)), dim3(XALL_NT), 0, s, ev, sv, (unsigned)p.xall_nd,
+                               (unsigned)env->tune.expand_dbl_npb, (unsigned)env->tune.expand_parts, more ? sv_next.tops : (unsigned long long *)nullptr,
                                (int)T_COUNT);
         }
-        // inside a run the apply of this step and the roots of the next share a launch; the counter set those roots allocate from is cleared
-        // earlier in THIS step, while nothing uses it: by the expansion launch (every value-net mode), else by the incremental value net
-        const bool fused = more && (incremental || env->expand_merged);
-        hipStream_t se = s;
-        if (incremental) {
+        // inside a run the apply of this step and the roots of the next share a launch (StepPlan::fused_with_more)
+        const bool fused = more && p.fused_with_more;
+        if (p.incremental) {
             if (own_root_launch && ss.root != s) HIPCHK(hipStreamWaitEvent(s, env->ev_join, 0));
-            KTimer t(env, se, 1);
-            // every workgroup first copies W1^T (117 KB) into LDS: small envs get only as many as their rows can use
-            long long dblocks = (n * 24 + DELTA_THREADS - 1) / DELTA_THREADS;
-            dblocks = dblocks < 1 ? 1 : (dblocks > ss.n_cu ? ss.n_cu : dblocks);
-#ifdef BGAMD_EXPERIMENTAL
-            if (env->mfma_delta && env->net.wm_ok[slot])
-                hipLaunchKernelGGL(eval_rows_mdelta_kernel, dim3((unsigned)dblocks), dim3(MD_THREADS), MD_LDS_TOTAL, se,
-                                   (const uint4 *)sv.u_rows, (const unsigned long long *)&sv.tops[T_U], (long long)sv.cap_rows, &env->v.counters[C_ROWS_EVAL],
-                                   (const uint4 *)env->net.d_wm[slot], w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden,
-                                   env->v.values, (const uint2 *)sv.u_info, sv.best, &env->v.counters[C_KSTEPS],
-                                   fused ? sv_next.tops : (unsigned long long *)nullptr, (int)T_COUNT, &env->v.counters[C_ERR],
-                                   (unsigned long long)ERRF_DELTA);
-            else
-#endif
-            hipLaunchKernelGGL(eval_rows_delta_kernel, dim3((unsigned)dblocks), dim3(DELTA_THREADS), DELTA_LDS_TOTAL, se,
-                               (const uint4 *)sv.u_rows, (const unsigned long long *)&sv.tops[T_U], (long long)sv.cap_rows, &env->v.counters[C_ROWS_EVAL],
-                               (const float4 *)env->net.d_wt[slot], w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden,
-                               env->v.values, (const uint2 *)sv.u_info, sv.best, &env->v.counters[C_KSTEPS],
-                               fused ? sv_next.tops : (unsigned long long *)nullptr, (int)T_COUNT, &env->v.counters[C_ERR],
-                               (unsigned long long)ERRF_DELTA, sv.b_base > 0 ? (const unsigned long long *)&sv.tops[T_UB] : (const unsigned long long *)nullptr,
-                               (long long)sv.b_base);                 // (the counters of arenas 1, 2, 3 follow one another from T_UB)
+            KTimer t(env, s, 1);
+            launch_delta(env, slot, p.mfma_delta, p.delta_grid, sv, &sv.tops[T_U], sv.cap_rows, env->v.values,
+                         fused ? sv_next.tops : (unsigned long long *)nullptr, s);
         } else {
-            const int rc = launch_eval(env, slot, precision, &sv.tops[T_U], sv.cap_rows, sv.u_rows, env->v.values, sv.u_info, sv.best, se);
+            const int rc = launch_eval(env, slot, precision, p.eval, &sv.tops[T_U], sv.cap_rows, sv.u_rows, env->v.values, sv.u_info, sv.best, s);
             if (rc) return rc;
         }
         // sampled step: sv.best[g] becomes the pack of the row drawn with probability ~ exp(value / T) (never for a scoring pass)
-        if (temperature > 0.0f && !score_only) launch_sample_passes(env, ev, sv.tops, sv.b_base, temperature, ss.n_cu, s);
+        if (temperature > 0.0f && !score_only) launch_sample_passes(env, ev, sv.tops, sv.b_base, temperature, p, s);
         ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
         if (epsilon > 0.0f) {                              // exploring lanes pick through their counted tasks (bounded work)
             KTimer t(env, s, 3);
             HIPCHK(hipMemsetAsync(env->rv.top, 0, 8, s));
             hipLaunchKernelGGL(rnd_tasks_kernel, grid1(n, 256), dim3(256), 0, s, ev, env->rv, flags & ~BGAMD_ROLL, epsilon);
-            long long b = (n * 4 + 255) / 256;
-            const long long lim = (long long)ss.n_cu * 8;
-            hipLaunchKernelGGL(rnd_count_kernel, dim3((unsigned)(b > lim ? lim : b)), dim3(256), 0, s, ev, env->rv);
+            hipLaunchKernelGGL(rnd_count_kernel, dim3((unsigned)p.rnd_count_grid), dim3(256), 0, s, ev, env->rv);
         }
         if (!score_only) {
             KTimer t(env, s, 2);
             ev.end_slot = ev.traj_ring ? cur_step % ev.traj_ring : 0;      // the apply half closes the step the last roots began
             if (fused) {
                 next_log_slot();                                           // ... and the roots half begins the next one
-                root_ready = incremental && env->root_in_boundary;
-#ifdef BGAMD_EXPERIMENTAL
-                if (env->root_f32_mfma || !env->root_resident) root_ready = false;          // (the other root passes exist as launches only)
-#endif
+                root_ready = p.root_in_boundary;
                 if (root_ready)
                     hipLaunchKernelGGL(boundary_kernel<true>, grid1(n, BROOT_GPW), dim3(LANE_NT), BROOT_LDS_BYTES, s, ev, sv, sv_next, xv, flags, epsilon,
-                                       env->net.root_w(slot), env->net.root_lut(), b1);
+                                       env->net.root_w(slot), env->net.root_lut(), env->net.b1(slot));
                 else
                     hipLaunchKernelGGL(boundary_kernel<false>, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, ev, sv, sv_next, xv, flags, epsilon,
                                        (const uint4 *)nullptr, (const uint2 *)nullptr, (const float *)nullptr);
@@ -1809,7 +1704,7 @@ int score_virtual_lanes(bgamd_env *env, int slot, long long n_virtual, const See
 int run_steps(GreedyRun &run, int64_t n_steps, hipStream_t s)
 {
     bgamd_env *env = run.env;
-    const StepStreams ss{s, (run.incremental && env->overlap) ? env->side : s, env->n_cu};
+    const StepStreams ss{s, (run.plan.incremental && env->tune.overlap) ? env->side : s};
     int rc = run.begin(s);
     if (rc) return rc;
     for (int64_t step = 0; step < n_steps; ++step) {
@@ -2264,7 +2159,7 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
     const RoView r{N, T, M, rotate ? 1 : 0, F, ro.pos, ro.fan, ro.fval, ro.lane, ro.tval, ro.tturns, ro.trows, ro.tids, ctr,
                    d_group ? (const int32_t *)ro.group : nullptr};
     const int run_flags = flags & BGAMD_WEIGHTS_SLOT1;
-    const StepStreams ss{s, sc->overlap ? sc->side : s, sc->n_cu};
+    const StepStreams ss{s, sc->tune.overlap ? sc->side : s};
     long long steps = 0;
 
     // plies = 2 (bgamd_env_rollout_policy): every turn is one filtered search step of the trial env.  Its virtual roots are scored on
@@ -2292,7 +2187,7 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
             hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, ro.fan);
             ++steps;
         }
-        if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, nullptr, n_fan, ro.fan, ro.fval, nullptr, nullptr, s))) return rc;
+        if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, eval_grids(n_fan, sc->n_cu), nullptr, n_fan, ro.fan, ro.fval, nullptr, nullptr, s))) return rc;
     }
 
     // luck adjustment: the pre-roll evaluation on the search's scratch env -- of the P positions once (rotation: turn 0's luck), then
@@ -2324,10 +2219,11 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
     }
     if (two_ply) R = 1;                                // a search turn is a step of its own: a refill after every turn
     const int G = R >= 16 ? 1 : 16 / R;                // runs between two reads of the trials-done counter (~16 turns)
+    const EvalGrids trunc_grids = eval_grids(sc->v.n * EST_ROWS, sc->n_cu);      // (the truncated rows are counted on the device: sized as a step's)
     auto refill = [&]() -> int {
         hipLaunchKernelGGL(ro_refill_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, r);
         if (M > 0) {                                   // truncated trials: the dense fp32 evaluator of bgamd_evaluate_slot
-            if (const int e = launch_eval(sc, slot, BGAMD_F32, &ctr[RO_NTRUNC], L, ro.trows, ro.tv, nullptr, nullptr, s)) return e;
+            if (const int e = launch_eval(sc, slot, BGAMD_F32, trunc_grids, &ctr[RO_NTRUNC], L, ro.trows, ro.tv, nullptr, nullptr, s)) return e;
             hipLaunchKernelGGL(ro_trunc_scatter_kernel, dim3((unsigned)sc->n_cu), dim3(RO_NT), 0, s, r, (const float *)ro.tv);
             HIPCHK(hipMemsetAsync(&ctr[RO_NTRUNC], 0, 8, s));
         }
@@ -2690,7 +2586,7 @@ int bgamd_evaluate_slot(bgamd_env *env, int slot, const int32_t *d_states28, con
     // the candidate arena doubles as scratch for caller-provided states
     hipLaunchKernelGGL(pack_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_turn, (long long)n, env->v.rows,
                        &env->v.counters[C_ERR]);
-    return launch_eval(env, slot, precision, nullptr, (long long)n, env->v.rows, d_values, nullptr, nullptr, s);
+    return launch_eval(env, slot, precision, eval_grids((long long)n, env->n_cu), nullptr, (long long)n, env->v.rows, d_values, nullptr, nullptr, s);
 }
 
 int bgamd_evaluate_incremental(bgamd_env *env, int slot, const int32_t *d_root_states28, const int32_t *d_root_turn,
@@ -2705,7 +2601,6 @@ int bgamd_evaluate_incremental(bgamd_env *env, int slot, const int32_t *d_root_s
     if (n == 0) return BGAMD_OK;
     hipStream_t s = (hipStream_t)stream;
     StagedView &sv = env->sv;
-    const float *w2 = env->net.w2(slot), *b2 = env->net.b2(slot);
     // the env's root / afterstate arenas double as scratch, as the candidate arena does for bgamd_evaluate; the rows are written
     // linearly from 0: a later unique_rows_read must not remap them through the arena counters of an earlier greedy step
     sv.b_base = 0;
@@ -2714,24 +2609,10 @@ int bgamd_evaluate_incremental(bgamd_env *env, int slot, const int32_t *d_root_s
     hipLaunchKernelGGL(pack_child_rows_kernel, grid1(n, 128), dim3(128), 0, s, d_states28, d_root_index, (long long)n,
                        (long long)n_roots, (const uint4 *)sv.root_rows, sv.u_rows, sv.u_info, &env->v.counters[C_ERR]);
     HIPCHK(hipMemsetAsync(sv.best, 0, (size_t)n_roots * 8, s));
-    launch_root_pass(env, slot, (const uint4 *)sv.root_rows, (long long)n_roots, sv.root_hidden, false, s);
-    long long dblocks = (n + DELTA_THREADS - 1) / DELTA_THREADS;
-    dblocks = dblocks < 1 ? 1 : (dblocks > env->n_cu ? env->n_cu : dblocks);
+    const RootPass root = root_pass_kind(env->tune, false);
+    launch_root_pass(env, slot, root, root_pass_grid(root, (long long)n_roots, env->n_cu), (const uint4 *)sv.root_rows, (long long)n_roots, sv.root_hidden, s);
     KTimer t(env, s, 1);
-#ifdef BGAMD_EXPERIMENTAL
-    if (env->mfma_delta && env->net.wm_ok[slot])
-        hipLaunchKernelGGL(eval_rows_mdelta_kernel, dim3((unsigned)dblocks), dim3(MD_THREADS), MD_LDS_TOTAL, s, (const uint4 *)sv.u_rows,
-                           (const unsigned long long *)nullptr, (long long)n, (unsigned long long *)nullptr, (const uint4 *)env->net.d_wm[slot],
-                           w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden, d_values, (const uint2 *)sv.u_info, sv.best,
-                           (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0, &env->v.counters[C_ERR],
-                           (unsigned long long)ERRF_DELTA);
-    else
-#endif
-    hipLaunchKernelGGL(eval_rows_delta_kernel, dim3((unsigned)dblocks), dim3(DELTA_THREADS), DELTA_LDS_TOTAL, s, (const uint4 *)sv.u_rows,
-                       (const unsigned long long *)nullptr, (long long)n, (unsigned long long *)nullptr, (const float4 *)env->net.d_wt[slot],
-                       w2, b2, (const uint4 *)sv.root_rows, (const float *)sv.root_hidden, d_values, (const uint2 *)sv.u_info, sv.best,
-                       (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0, &env->v.counters[C_ERR],
-                       (unsigned long long)ERRF_DELTA, (const unsigned long long *)nullptr, 0ll);
+    launch_delta(env, slot, env->tune.mfma_delta && env->net.wm_ok[slot], delta_grid((long long)n, env->n_cu), sv, nullptr, (long long)n, d_values, nullptr, s);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
@@ -2756,22 +2637,14 @@ int bgamd_env_time_kernels(bgamd_env *env, int enable)
 
 const char *bgamd_build_flags(void)
 {
-#ifdef BGAMD_EXPERIMENTAL
-    return "experimental";
-#else
-    return "default";
-#endif
+    return EXPERIMENTAL_BUILD ? "experimental" : "default";
 }
 
 int bgamd_env_kernel_choice(bgamd_env *env, int32_t h_out[4])
 {
     if (!env || !h_out) return BGAMD_E_INVALID;
     for (int i = 0; i < 3; ++i) h_out[i] = env->choice[i];
-#ifdef BGAMD_EXPERIMENTAL
-    h_out[3] = 1;
-#else
-    h_out[3] = 0;
-#endif
+    h_out[3] = EXPERIMENTAL_BUILD ? 1 : 0;
     return BGAMD_OK;
 }
 
