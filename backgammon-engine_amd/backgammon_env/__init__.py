@@ -304,15 +304,29 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_sample_info(self._h, h), "sample_info")
         return list(h)
 
-    def step_search(self, top_k=8, roll=True, auto_reset=True, no_flip=False, want_index=False, only_player=None, slot=0, margin=None):
+    def step_search(self, top_k=8, roll=True, auto_reset=True, no_flip=False, want_index=False, only_player=None, slot=0, margin=None,
+                    plies=2, deep_k=2, deep_margin=float("inf"), reply_top_k=2, reply_margin=float("inf")):
         """One 2-ply expectimax turn (include/bgamd.h, bgamd_env_step_search): the top_k best afterstates by the net (0 = all
         distinct ones) are re-scored by the average over the opponent's 21 rolls of the opponent's greedy reply, and the best of
         them is played.  last_choice()["value"] is that 2-ply value; search_candidates() lists the kept candidates.
         margin (None = the step above): the filtered step (bgamd_env_step_search_filtered) -- only the candidates whose 1-ply value lies
         within `margin` (>= 0, may be inf) of the best are searched, and a lane that keeps one candidate plays it unsearched (its value
-        and v2 are its 1-ply value).  Synchronises once."""
+        and v2 are its 1-ply value).  Synchronises once.
+        plies = 3 (bgamd_env_step_search3): the filtered step (margin None = inf) whose best candidates by the 2-ply value -- at most
+        deep_k (0 = all), within deep_margin of the best -- are searched one ply deeper: the opponent answers each of its 21 rolls with
+        the best of its reply_top_k (0 = all) replies within reply_margin by THEIR 2-ply value.  last_choice()["value"] is the deepest value
+        the chosen move received; search_candidates() adds v3 and depth, search3_info() counts the work.  Synchronises twice and once per
+        chunk of the mid level.  The deep parameters are ignored at plies = 2."""
         flags = self._flags(roll, auto_reset, no_flip, only_player, slot) | (WANT_INDEX if want_index else 0)
-        if margin is None:
+        if plies not in (2, 3):
+            raise ValueError("plies must be 2 or 3")
+        self._search_plies = 2
+        if plies == 3:
+            _capi.check(self._lib.bgamd_env_step_search3(self._h, flags, int(top_k), float("inf") if margin is None else float(margin),
+                                                         int(deep_k), float(deep_margin), int(reply_top_k), float(reply_margin), _stream()),
+                        "step_search3")
+            self._search_plies = 3
+        elif margin is None:
             _capi.check(self._lib.bgamd_env_step_search(self._h, flags, int(top_k), _stream()), "step_search")
         else:
             _capi.check(self._lib.bgamd_env_step_search_filtered(self._h, flags, int(top_k), float(margin), _stream()), "step_search_filtered")
@@ -325,9 +339,19 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_search_info(self._h, h), "search_info")
         return list(h)
 
+    def search3_info(self):
+        """Host values of the last 3-ply search step (bgamd_env_search3_info; synchronises): [lanes that had a move, lanes searched at 2
+        plies, lanes searched at 3 plies, deep candidates, mid lanes, level-3 virtual roots scored].  Raises unless the last search step
+        was a 3-ply one."""
+        h = (C.c_int64 * 6)()
+        _capi.check(self._lib.bgamd_env_search3_info(self._h, h), "search3_info")
+        return list(h)
+
     def search_candidates(self):
         """The last search step's kept candidates, best 1-ply value first: (states[n,K,28], v1[n,K], v2[n,K], kept[n]); K is
-        that step's top_k, or (top_k = 0) the largest kept count.  Slots past a lane's count are zero."""
+        that step's top_k, or (top_k = 0) the largest kept count.  Slots past a lane's count are zero.  After a 3-ply step
+        (step_search(plies=3)) two more follow: v3[n,K] (0 where depth < 3) and depth[n,K] int32, the deepest value the candidate
+        received: 1, 2 or 3, and 0 past the lane's count."""
         kept = self._buf((self.n,), torch.int32)
         _capi.check(self._lib.bgamd_env_search_read(self._h, None, None, None, _ptr(kept), _stream()), "search_read")
         K = getattr(self, "_search_k", 0)
@@ -337,6 +361,10 @@ class VecGame:
         v1, v2 = self._buf((self.n, K), torch.float32), self._buf((self.n, K), torch.float32)
         if K > 0:
             _capi.check(self._lib.bgamd_env_search_read(self._h, _ptr(st), _ptr(v1), _ptr(v2), None, _stream()), "search_read")
+        if getattr(self, "_search_plies", 2) == 3:
+            v3, depth = self._buf((self.n, K), torch.float32), self._buf((self.n, K), torch.int32)
+            _capi.check(self._lib.bgamd_env_search3_read(self._h, _ptr(v3), _ptr(depth), _stream()), "search3_read")
+            return st, v1, v2, kept, v3, depth
         return st, v1, v2, kept
 
     ANALYSIS_FIELDS = (("status", torch.int32), ("distinct", torch.int32), ("rank1", torch.int32), ("rank2", torch.int32),

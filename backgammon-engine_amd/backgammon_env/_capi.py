@@ -68,6 +68,9 @@ SYMBOLS = [
     ("bgamd_env_search_read", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("bgamd_env_step_search_filtered", C.c_int, [_P, C.c_int, C.c_int, C.c_float, _P]),
     ("bgamd_env_search_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("bgamd_env_step_search3", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, _P]),
+    ("bgamd_env_search3_read", C.c_int, [_P, _P, _P, _P]),
+    ("bgamd_env_search3_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("bgamd_env_set_search_log", C.c_int, [_P, _P, _P, _P, _P, C.c_int64]),
     ("bgamd_env_analyze_moves", C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     ("bgamd_env_analysis_read", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -11,7 +11,7 @@
 //   stage D  srch_reduce (lane per game): V2 in the fixed roll order, arg-best, the winner's key into sv.best -> apply_kernel
 #pragma once
 
-constexpr int SRCH_ROLLS = 21;
+#include "bg_search_order.h"              // SRCH_ROLLS, srch_pack: shared with the 3-ply step's kernels, which are compiled apart
 // (SRCH_NT = 256 threads per workgroup: bg_step_plan.h)
 
 // the 21 unordered rolls in the fixed order (1,1), (1,2), ..., (1,6), (2,2), ..., (6,6)
@@ -117,13 +117,6 @@ __device__ __forceinline__ SrchCand srch_cand(const uint4 *__restrict__ rows, co
     c.term = off15 != 0;
     c.v = c.term ? (mover ? 0.0f : 1.0f) : values[row];
     return c;
-}
-// larger = better for the mover, then smaller key (the greedy step's best_atomic_max order)
-__device__ __forceinline__ unsigned long long srch_pack(float v, uint32_t key, int mover)
-{
-    uint32_t bits = __float_as_uint(v);
-    bits = mover ? ~bits : bits;
-    return ((unsigned long long)bits << 32) | (uint32_t)~key;
 }
 __device__ __forceinline__ bool srch_same(const uint32_t (&x)[8], const uint32_t (&y)[8])
 {

@@ -47,6 +47,7 @@ constexpr bool EXPERIMENTAL_BUILD = false;
 #include "bg_step_plan.h"
 #include "bg_movegen.h"
 #include "bg_staged.h"
+#include "bg_search3.h"
 
 using namespace bg;
 
@@ -750,6 +751,32 @@ struct SearchState {
     hipStream_t stream = nullptr;
     bool info_read = false;
     int64_t info[4] = {0, 0, 0, 0};
+    // the 3-ply step (bg_search3.h), allocated by the first one: dkept [n] = |L2| of the lanes searched deeper (else 0), doff [n + 1] its
+    // scan; per candidate [d_cap] c_d3 (rank in L2 or -1), c_v3, dmap (the deep list), r3 [d_cap][21] the mid roots' values; d_info3 [6],
+    // d_l3 the count of level-3 roots.  deep: the last search step was a 3-ply one (bgamd_env_search3_read / _info)
+    uint32_t *dkept = nullptr, *doff = nullptr, *dmap = nullptr;
+    int32_t *c_d3 = nullptr;
+    float *c_v3 = nullptr, *r3 = nullptr;
+    unsigned long long *d_info3 = nullptr, *d_l3 = nullptr;
+    long long d_cap = 0;
+    float *pass_v1 = nullptr;              // a MID env's: [n] the value srch_collect_kernel forms per lane, the pass reply's v1
+    bool deep = false, info3_read = false;
+    int64_t info3[6] = {0, 0, 0, 0, 0, 0};
+};
+
+// what bgamd_env_step_search3 adds to the filtered step's arguments
+struct Search3Params {
+    int deep_k;
+    float deep_margin;
+    int reply_top_k;
+    float reply_margin;
+};
+// a search of the 3-ply step's mid env (search_stages): the mid lanes are mid roots v0 .. of r3; roots counts the level-3 virtual roots
+struct Search3Mid {
+    s3::DeepList deep;
+    float *r3;
+    long long v0;
+    unsigned long long *roots;
 };
 
 // search log (bgamd_env_set_search_log, bg_search_log.h): the caller's buffers, [plies][n] each; rows NULL = no log
@@ -829,6 +856,10 @@ struct bgamd_env {
     // The analysis features run the greedy step's kernels on internal envs (scratch_env): `scratch` holds the virtual roots the 2-ply search
     // and the pre-roll evaluation score, `rscratch` plays the rollout's trials.  Such an env has no tables of its own: its `net` is its parent's.
     bgamd_env *scratch = nullptr, *rscratch = nullptr;
+    // the 3-ply step's mid env (bg_search3.h): one lane per (deep candidate, opponent roll), searched with `scratch` lent to it.  Created by
+    // the first 3-ply step, with at most mid_chunk lanes (SEARCH3_CHUNK, or the test hook BGAMD_SEARCH3_CHUNK read then)
+    bgamd_env *mid = nullptr;
+    long long mid_chunk = 0;
     // [A_WORDS]: the rollout's counters (RoView::ctr), then the word that takes the bad-state bit of intake_positions -- one allocation, a
     // whole number of 16-byte units, so that the rollout's one fill launch clears both.  48 bytes, allocated with every env (env_allocate).
     unsigned long long *a_ctr = nullptr;
@@ -1073,6 +1104,7 @@ int bgamd_env_destroy(bgamd_env *env)
     hipDeviceSynchronize();
     if (env->scratch) bgamd_env_destroy(env->scratch);            // (on this device too; each frees what its own owner handed out)
     if (env->rscratch) bgamd_env_destroy(env->rscratch);
+    if (env->mid) bgamd_env_destroy(env->mid);
     env->mem.release_all();
     for (hipEvent_t e : env->ev) hipEventDestroy(e);
     for (hipEvent_t e : {env->ev_fork, env->ev_join, env->ro.ev[0], env->ro.ev[1]}) if (e) hipEventDestroy(e);
@@ -1820,7 +1852,13 @@ static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int
 // matched and forced into the kept set, and in place of the choice and the apply launch the per-lane results and their summary.
 // margin NULL: every candidate of the top_k is searched, as ever.  Else the filtered step (bg_filter.h, search step only): the margin
 // rule in the selection, no virtual root for a lane that keeps one candidate, and scoring passes for the list's real length.
-static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, const float *margin, hipStream_t s)
+// deep (search step, filtered): the 3-ply step (bg_search3.h) -- between the filtered step's reduce and the apply, search3_deep searches
+// the deep set one ply further and rewrites best[g] of the lanes it searched.  mid (filtered, no apply): the search of that step's mid env
+// -- the pass reply, every kept reply searched, the best V2 of every mid lane into mid->r3.  With both NULL the launches are what they
+// were before either existed.
+static int search3_deep(bgamd_env *env, int slot, const Search3Params &p, hipStream_t s);
+static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, const float *margin, hipStream_t s,
+                         const Search3Params *deep = nullptr, const Search3Mid *mid = nullptr)
 {
     if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
     // ... into those two.  Its own log (bgamd_env_set_search_log) is written by the search step alone; the analysis applies nothing and
@@ -1855,6 +1893,7 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
     long long n_cand = top_k > 0 && !margin ? n * (long long)(top_k + (d_played ? 1 : 0)) : 0;
     if (n_cand > 0 && (rc = grow_candidates(n_cand))) return rc;
     se.k = -1;
+    se.deep = false;
 
     // stage A: the greedy step's roots, expansion and incremental value net, no apply
     GreedyRun run;
@@ -1883,16 +1922,19 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
     else
         hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
                            (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept);
+    if (mid)                                           // a mid lane without rows keeps its pass reply
+        s3::reply_fix(s, n, mid->v0, mid->deep, (const uint32_t *)se.cnt, se.kept);
     hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.kept, se.koff, n, se.max);
     int K = top_k;
     long long n_searched = 0;                          // filtered step: the searched candidates (those of the lanes that kept >= 2)
-    if (margin)
+    const bool singletons_skipped = margin && !mid;    // (the mid env searches every kept reply: its searched list is its candidate list)
+    if (singletons_skipped)
         hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.skept, se.soff, n, (uint32_t *)nullptr);
     if (margin || top_k == 0) {                        // the list's length is not known here (filtered, or every distinct afterstate): it is read
         uint32_t h[3] = {0, 0, 0};                     // back, with the searched list's when filtered (the one synchronisation)
         HIPCHK(hipMemcpyAsync(&h[0], se.koff + n, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&h[1], se.max, 4, hipMemcpyDeviceToHost, s));
-        if (margin) HIPCHK(hipMemcpyAsync(&h[2], se.soff + n, 4, hipMemcpyDeviceToHost, s));
+        if (singletons_skipped) HIPCHK(hipMemcpyAsync(&h[2], se.soff + n, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         n_cand = h[0]; n_searched = h[2];
         if (top_k == 0) K = (int)h[1];
@@ -1902,10 +1944,17 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
     hipLaunchKernelGGL(srch_emit_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
                        (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, (const int32_t *)se.rank,
                        (const uint32_t *)se.koff, se.c_rows, se.c_key, se.c_v1);
+    if (mid && n_cand > 0) {                           // the pass replies: v1 as srch_collect_kernel forms the value of a lane without a move
+        if (!se.pass_v1 && (rc = env->mem.alloc(BG_BUF(se.pass_v1, (size_t)n * 4)))) return rc;
+        hipLaunchKernelGGL(srch_collect_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, (const unsigned long long *)env->sv.best,
+                           (const float *)env->sv.root_hidden, env->net.w2(run.slot), env->net.b2(run.slot), 0ll, se.pass_v1);
+        s3::pass_emit(s, n, mid->v0, mid->deep, (const uint32_t *)se.cnt, (const uint32_t *)se.koff, (const float *)se.pass_v1, se.c_rows,
+                      se.c_key, se.c_v1);
+    }
 
     // stage C: one virtual lane per (candidate, opponent roll), scored on the scratch env
-    const long long n_virtual = (margin ? n_searched : n_cand) * SRCH_ROLLS;
-    if (margin && n_virtual > 0) {
+    const long long n_virtual = (singletons_skipped ? n_searched : n_cand) * SRCH_ROLLS;
+    if (singletons_skipped && n_virtual > 0) {
         hipLaunchKernelGGL(flt_vmap_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
                            (const uint32_t *)se.koff, (const uint32_t *)se.soff, se.vmap);
         if ((rc = scratch_env(env, &env->scratch, search_lanes(n_virtual), false, 0, s))) return rc;
@@ -1934,6 +1983,12 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
         an.ready = true;
         return BGAMD_OK;
     }
+    if (mid) {                                         // the mid env's stage D: the best searched reply of every mid lane, nothing applied
+        s3::r3_reduce(s, n, mid->v0, mid->deep, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.c_key,
+                      (const float *)se.c_v1, (const float *)se.c_rval, se.c_v2, mid->r3, mid->roots, &env->v.counters[C_ERR], scratch_err);
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    }
     // stage D: V2, choice, and the greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice)
     if (margin)
         hipLaunchKernelGGL(flt_reduce_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
@@ -1947,6 +2002,7 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
         hipLaunchKernelGGL(srch_log_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, flags, (const uint4 *)env->sv.root_rows,
                            (const unsigned long long *)env->sv.best, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows,
                            (const uint32_t *)se.c_key, (const float *)se.c_v1, (const float *)se.c_v2, margin ? 2u : 1u, env->slog);
+    if (deep && (rc = search3_deep(env, run.slot, *deep, s))) return rc;
     const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
     hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
     HIPCHK(hipGetLastError());
@@ -1954,6 +2010,113 @@ static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_
     se.min_searched = margin ? 2u : 1u;
     se.stream = s;
     se.info_read = false;
+    se.deep = deep != nullptr;
+    se.info3_read = false;
+    return BGAMD_OK;
+}
+
+// ---- the 3-ply step's deep level (bg_search3.h) ---------------------------------------------------------------------------------------
+// Mid lanes per chunk: the mid env has at most this many lanes (~1.8 GB at 65 536, its search buffers included).  A chunk costs ~1.5 ms
+// beside its scoring passes (its launches and its one synchronisation): at 16 384 lanes per chunk a 16 384-lane step took 74 ms, at
+// 65 536 it takes 49 ms (profiles/search3.txt).  Every mid lane is searched on its own, so no result depends on it; BGAMD_SEARCH3_CHUNK
+// (a multiple of 256) overrides it for the tests.
+constexpr long long SEARCH3_CHUNK = 65536;
+
+// env holds a filtered step's kept lists, V2 and best[g].  Selects the deep set of every searched lane, searches its (candidate, opponent
+// roll) mid lanes on env->mid a chunk at a time -- env->scratch lent to it for the virtual roots, as the 2-ply rollouts lend it -- and
+// leaves best[g] of the lanes searched deeper as their V3 choice.  Synchronises s once for the deep list's length and once per mid chunk.
+static int search3_deep(bgamd_env *env, int slot, const Search3Params &p, hipStream_t s)
+{
+    SearchState &se = env->srch;
+    const long long n = env->v.n;
+    int rc;
+    if (!se.dkept) {                                   // all or none: dkept != NULL says that every buffer is there
+        const size_t per_game = (size_t)(n + 1) * 4;
+        if ((rc = env->mem.alloc_group({BG_BUF(se.dkept, per_game), BG_BUF(se.doff, per_game), BG_BUF(se.d_info3, 6 * 8), BG_BUF(se.d_l3, 8)})))
+            return rc;
+    }
+    if ((rc = env->mem.grow(se.c_cap, se.d_cap, {BG_BUF(se.c_d3, 4), BG_BUF(se.c_v3, 4), BG_BUF(se.dmap, 4), BG_BUF(se.r3, 4 * SRCH_ROLLS)})))
+        return rc;
+    HIPCHK(hipMemsetAsync(se.d_l3, 0, 8, s));
+    s3::deep_select(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key,
+                    (const float *)se.c_v2, p.deep_k > 0 ? (uint32_t)p.deep_k : 0xFFFFFFFFu, p.deep_margin, se.c_d3, se.dkept);
+    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.dkept, se.doff, n, (uint32_t *)nullptr);
+    uint32_t n_deep = 0;
+    HIPCHK(hipMemcpyAsync(&n_deep, se.doff + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (n_deep == 0) return BGAMD_OK;                  // no lane is searched deeper: the filtered step's choices stand
+    s3::deep_map(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept, (const uint32_t *)se.doff,
+                 (const int32_t *)se.c_d3, se.dmap);
+
+    const long long n_mid = (long long)n_deep * SRCH_ROLLS;
+    if (!env->mid_chunk) {
+        env->mid_chunk = SEARCH3_CHUNK;
+        if (const char *h = getenv("BGAMD_SEARCH3_CHUNK")) {
+            const long long c = atoll(h);
+            if (c >= 256 && c % 256 == 0) env->mid_chunk = c;
+        }
+    }
+    const long long want = n_mid < env->mid_chunk ? ((n_mid + 255) / 256) * 256 : env->mid_chunk;
+    if ((rc = scratch_env(env, &env->mid, want, false, 0, s))) return rc;
+    bgamd_env *mid = env->mid;
+    for (long long v0 = 0; v0 < n_mid; v0 += mid->v.n) {
+        hipLaunchKernelGGL(flt_fanout_kernel<SRCH_NT>, grid1(mid->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, mid->v, v0, (const uint32_t *)(se.doff + n),
+                           (const uint32_t *)se.dmap, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
+        const Search3Mid out{{se.doff + n, se.dmap, se.c_rows, se.c_key}, se.r3, v0, se.d_l3};
+        mid->scratch = env->scratch;
+        rc = search_stages(mid, slot ? BGAMD_WEIGHTS_SLOT1 : 0, p.reply_top_k, nullptr, &p.reply_margin, s, nullptr, &out);
+        env->scratch = mid->scratch;                   // (re-created if it had to grow)
+        mid->scratch = nullptr;
+        if (rc) return rc;
+    }
+    s3::v3_reduce(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept, (const uint32_t *)se.doff,
+                  (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1, (const int32_t *)se.c_d3, (const float *)se.r3,
+                  se.c_v3, env->sv.best, &env->v.counters[C_ERR], &mid->v.counters[C_ERR]);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_step_search3(bgamd_env *env, int flags, int top_k, float margin, int deep_k, float deep_margin, int reply_top_k,
+                           float reply_margin, void *stream)
+{
+    if (!env || top_k < 0 || deep_k < 0 || reply_top_k < 0 || !(margin >= 0.0f) || !(deep_margin >= 0.0f) || !(reply_margin >= 0.0f))
+        return BGAMD_E_INVALID;                                          // (a NaN margin fails its comparison)
+    if (env->slog.rows) return BGAMD_E_INVALID;                          // 3-ply targets are not logged: refused, not written half-right
+    HIPCHK(hipSetDevice(env->device));
+    const Search3Params p{deep_k, deep_margin, reply_top_k, reply_margin};
+    return search_stages(env, flags, top_k, nullptr, &margin, (hipStream_t)stream, &p);
+}
+
+int bgamd_env_search3_read(bgamd_env *env, float *d_v3, int32_t *d_depth, void *stream)
+{
+    ENV_GUARD(env);
+    const SearchState &se = env->srch;
+    if (se.k < 0 || !se.deep) return BGAMD_E_INVALID;
+    const long long n = env->v.n, K = se.k;
+    if (K > 0 && (d_v3 || d_depth))
+        s3::read((hipStream_t)stream, n, (int)K, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept,
+                 (const int32_t *)se.c_d3, (const float *)se.c_v3, d_v3, d_depth);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+// taken when asked for, on the stream of the step it describes, as bgamd_env_search_info
+int bgamd_env_search3_info(bgamd_env *env, int64_t h_out[6])
+{
+    ENV_GUARD(env);
+    SearchState &se = env->srch;
+    if (!h_out || se.k < 0 || !se.deep) return BGAMD_E_INVALID;
+    if (!se.info3_read) {
+        unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+        s3::info(se.stream, (long long)env->v.n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept,
+                 (const uint32_t *)se.c_key, (const int32_t *)se.c_d3, (const unsigned long long *)se.d_l3, se.d_info3);
+        HIPCHK(hipMemcpyAsync(h, se.d_info3, 6 * 8, hipMemcpyDeviceToHost, se.stream));
+        HIPCHK(hipStreamSynchronize(se.stream));
+        for (int q = 0; q < 6; ++q) se.info3[q] = (int64_t)h[q];
+        se.info3_read = true;
+    }
+    for (int q = 0; q < 6; ++q) h_out[q] = se.info3[q];
     return BGAMD_OK;
 }
 

@@ -276,6 +276,64 @@ int bgamd_env_step_search_filtered(bgamd_env *env, int flags, int top_k, float m
  * values without a launch): a search step launches nothing for them. */
 int bgamd_env_search_info(bgamd_env *env, int64_t h_out[4]);
 
+/* ---- the 3-ply search step: the opponent's replies chosen by 2-ply search -----------------------------------------------------------
+ * The filtered step, whose best candidates by V2 are searched one ply deeper.  Flags are the filtered step's, with the same meaning; the
+ * F32 incremental value net only; the weight slot by BGAMD_WEIGHTS_SLOT1.  For every live lane that takes part, mover m, opponent o:
+ *   1. plies 1 and 2 are bgamd_env_step_search_filtered(top_k, margin), launch for launch: roll, enumerate, v1 of every distinct afterstate,
+ *      the kept list L1, V2 of every candidate of a lane that kept >= 2; terminal candidates at their exact outcome, rank 0 always kept.  A
+ *      lane that keeps one candidate plays it unsearched, value = v1;
+ *   2. the deep set L2 of a searched lane: L1 ranked by (V2 for the mover, smaller key); d2(c) = ONE fp32 subtraction of V2(c) from
+ *      V2(rank 0) on the mover's side, never negative; c is kept iff its rank < deep_k (0 = no limit) AND d2(c) <= deep_margin; rank 0 is
+ *      always in.  A lane whose L2 has one member plays it -- it is the filtered step's choice --, its value is its V2, and no deeper root
+ *      is spent on it;
+ *   3. V3(c) for c in L2 when |L2| >= 2: a terminal c keeps its exact outcome; otherwise V3(c) = (sum over the 6 doubles of R3(c, r) + 2 x
+ *      sum over the 15 other rolls) / 36 in fp32, each part in roll order -- item 4's expression of the 2-ply search, so equal replies of
+ *      1.0 or 0.0 give exactly that;
+ *   4. R3(c, r), the opponent's SEARCHED reply from c with roll r:
+ *      - the replies are the distinct afterstates of (c, o to move, dice r); when o has no legal move the one reply is c itself (the pass),
+ *        which a doubles roll without a move yields as a row everywhere and this step adds for the other rolls;
+ *      - v1 of a reply d: the greedy step's value with o's turn bit, the exact outcome if o has borne off its 15th checker; for the pass
+ *        reply the net's value of c with o's turn bit;
+ *      - kept replies: the filter's rule with o as the mover -- rank in the (v1 for o, smaller key) order < reply_top_k (0 = all) and
+ *        within reply_margin of rank 0;
+ *      - EVERY kept reply, a single one too, gets V2(d) as item 4 of the 2-ply search defines it with the roles swapped: m's 21 rolls,
+ *        m's greedy reply or m's no-move value, the same fp32 sum; a terminal d takes its outcome;
+ *      - R3(c, r) = the best V2(d) for o over the kept replies: max for PLAYER1, min for PLAYER2;
+ *      - R3 depends on (c, r), the weights, reply_top_k and reply_margin alone: not on the lane, the other lanes, the other parameters or
+ *        the chunking;
+ *   5. choose the member of L2 with the best V3 for the mover (ties: the smaller key); apply, terminal check, flip or auto-reset by the
+ *      greedy step's own apply; bgamd_env_last_choice reports the chosen sequence and its deepest value: V3, or V2 / v1 for the lanes of
+ *      items 2 / 1;
+ *   6. bgamd_env_search_read and bgamd_env_search_info work after this step exactly as after the filtered step with the same (top_k,
+ *      margin): the 2-ply part is bit-identical to it.
+ * BGAMD_E_INVALID: a negative top_k, deep_k or reply_top_k; a NaN or negative margin of the three (+inf is allowed); a trajectory or ring
+ * log set (the search step's refusal); a SEARCH LOG set -- 3-ply targets are not logged, and the step refuses rather than write them
+ * half-right.  BGAMD_E_NOWEIGHTS, arena and delta errors surface as for the search step; error bits raised on the internal envs reach
+ * this env's.
+ * Synchronisation: the step SYNCHRONISES the stream 2 + C times: once as the filtered step does, once for the length of the deep list, and
+ * once in each of the C chunks of the mid level (below) for the length of its reply list; a step in which no lane is searched deeper
+ * synchronises twice.
+ * Device memory: the mid level -- one lane per (deep candidate, opponent roll) -- lives on an internal mid env of at most 65 536 lanes
+ * (~1.8 GB with its search buffers at that size; a smaller step creates a smaller one), created by the first 3-ply step and freed by
+ * bgamd_env_destroy; C = ceil(21 x deep candidates / its lanes).  Its (reply, roll) virtual roots are scored on the scratch env of the
+ * 2-ply search, which the step shares.  Per kept candidate the step adds 96 bytes (V3, the rank in L2, the deep list, 21 R3 values).
+ * Out of scope: bgamd_env_analyze_moves judges by 2 plies; bgamd_env_rollout_policy(plies = 3) stays refused; nothing samples; the
+ * search log is refused (above). */
+int bgamd_env_step_search3(bgamd_env *env, int flags, int top_k, float margin, int deep_k, float deep_margin, int reply_top_k,
+                           float reply_margin, void *stream);
+/* Aligned with bgamd_env_search_read's slots after a 3-ply step: d_depth [n,K] = the deepest value the candidate received -- 1 (a
+ * singleton's candidate), 2, or 3 (a member of L2 of a lane with |L2| >= 2) -- and 0 past a lane's kept count; d_v3 [n,K] = V3 where
+ * depth = 3, else 0.  Either pointer may be NULL.  BGAMD_E_INVALID before the first 3-ply step, and after a later search step of another
+ * kind or an analysis has overwritten the search state. */
+int bgamd_env_search3_read(bgamd_env *env, float *d_v3 /*[n,K]*/, int32_t *d_depth /*[n,K]*/, void *stream);
+/* Host values of the last 3-ply step (refused as bgamd_env_search3_read is; taken when asked for, as bgamd_env_search_info: one small
+ * launch on the step's stream, which is SYNCHRONISED):
+ *   h_out[0] lanes that had a move;   h_out[1] lanes searched at 2 plies (kept >= 2);   h_out[2] lanes searched at 3 plies (|L2| >= 2);
+ *   h_out[3] deep candidates = the members of L2 of the lanes of h_out[2];
+ *   h_out[4] mid lanes = 21 x the non-terminal ones of those;
+ *   h_out[5] level-3 virtual roots scored = 21 x the non-terminal kept replies of all mid lanes. */
+int bgamd_env_search3_info(bgamd_env *env, int64_t h_out[6]);
+
 /* ---- search log: the search steps' turns for the learner (TD replay of searched games, fitting the net to its own search) ------------
  * d_rows and d_after are [max_plies][n] x 32 B rows (16-byte aligned) in the trajectory log's format (8 planes, turn in plane 0 bit 31);
  * d_target and d_v1 are [max_plies][n] floats.  d_rows == NULL disables the log; with d_rows set any of the other three may be NULL (that

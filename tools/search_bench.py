@@ -7,7 +7,13 @@ starting positions: ms per step, the virtual roots scored, the lanes searched an
 (bgamd_env_search_info), and the share of lanes whose choice differs from the unfiltered step's on one common set of positions and dice.
 
 --log: what the search log's pass (bgamd_env_set_search_log, csrc/bg_search_log.h) costs a step -- the filtered step at 65 536 lanes,
-top_k 5, margin 0.04, without auto-reset, from the same positions with and without the log set, alternating; one JSON line."""
+top_k 5, margin 0.04, without auto-reset, from the same positions with and without the log set, alternating; one JSON line.
+
+--plies 3: the 3-ply step (bgamd_env_step_search3) instead -- per size and top_k, with --margin's first margin (default 0.04) and
+--deep-k / --deep-margin / --reply-k / --reply-margin: ms per step, ms per level-3 root, the mid lanes, the level-3 roots and the lanes
+searched at 3 plies of the last step (bgamd_env_search3_info), and the share of lanes whose choice differs from the filtered 2-ply step's
+on one common set of positions and dice.  The filtered 2-ply step with the same (top_k, margin) is timed in the same session from the same
+starting positions: it is the yardstick."""
 import argparse
 import json
 import os
@@ -74,6 +80,48 @@ def log_cost(a):
                                           "regions_ms_with": [round(x, 4) for x in ms[True]]}}))
 
 
+def three_plies(a):
+    import backgammon_env as bg
+    w = np.fromfile(os.path.join(ROOT, "tests", "golden", "tdgammonNEW100k.f32"), dtype=np.float32)
+    mg = [float(x) for x in a.margin.split(",") if x][0] if a.margin else 0.04
+    deep = dict(deep_k=a.deep_k, deep_margin=a.deep_margin, reply_top_k=a.reply_k, reply_margin=a.reply_margin)
+    out = []
+    for n in [int(x) for x in a.sizes.split(",")]:
+        env = bg.VecGame(n, seed=1)
+        env.load_weights(w)
+        for k in [int(x) for x in a.ks.split(",")]:
+            def start():
+                env.reset()
+                env.run_greedy(10)                     # positions past the opening
+            start()
+            f_ms, f_all = _time(lambda: env.step_search(top_k=k, margin=mg), a.steps, a.warmup, a.regions)
+            f_info = env.search_info()
+            start()
+            ms, all_ms = _time(lambda: env.step_search(top_k=k, margin=mg, plies=3, **deep), a.steps, a.warmup, a.regions)
+            info = env.search3_info()
+            # the choices of both steps on one set of positions and dice (nothing flips or restarts: the boards are the choices)
+            start()
+            env.roll()
+            st, tu, dice = env.states().clone(), env.turns().clone(), env.dice().clone()
+            env.step_search(top_k=k, roll=False, auto_reset=False, no_flip=True, margin=mg)
+            two = env.states().clone()
+            env.set_states(st, tu)
+            env.set_dice(dice)
+            env.step_search(top_k=k, roll=False, auto_reset=False, no_flip=True, margin=mg, plies=3, **deep)
+            differs = float((env.states() != two).any(1).float().mean())
+            r = {"n": n, "plies": 3, "top_k": k, "margin": mg, **deep, "ms_per_search_step": round(ms, 4),
+                 "filtered_2ply_ms_per_search_step": round(f_ms, 4), "times_the_2ply_step": round(ms / f_ms, 2),
+                 "lanes_with_a_move": info[0], "lanes_searched_2_plies": info[1], "lanes_searched_3_plies": info[2],
+                 "deep_candidates": info[3], "mid_lanes_last_step": info[4], "level3_roots_last_step": info[5],
+                 "ns_per_level3_root": round(ms * 1e6 / max(info[5], 1), 3), "virtual_roots_2ply_last_step": f_info[3],
+                 "ns_per_2ply_root": round(f_ms * 1e6 / max(f_info[3], 1), 3), "choice_differs_from_2ply_share": round(differs, 5),
+                 "regions_ms": [round(x, 4) for x in all_ms], "filtered_2ply_regions_ms": [round(x, 4) for x in f_all]}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+        env.close()
+    print(json.dumps({"search_bench_3_plies": out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="4096,16384,65536")
@@ -83,7 +131,14 @@ def main():
     ap.add_argument("--regions", type=int, default=5)
     ap.add_argument("--margin", default="", help="comma-separated margins of the filtered step (none: the unfiltered step only)")
     ap.add_argument("--log", action="store_true", help="the cost of the search log's pass instead (see above)")
+    ap.add_argument("--plies", type=int, default=2, choices=(2, 3), help="3: the 3-ply step against the filtered 2-ply step (see above)")
+    ap.add_argument("--deep-k", type=int, default=2)
+    ap.add_argument("--deep-margin", type=float, default=0.04)
+    ap.add_argument("--reply-k", type=int, default=2)
+    ap.add_argument("--reply-margin", type=float, default=0.04)
     a = ap.parse_args()
+    if a.plies == 3:
+        return three_plies(a)
     if a.log:
         return log_cost(a)
     import backgammon_env as bg
