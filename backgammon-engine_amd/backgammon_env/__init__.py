@@ -13,6 +13,7 @@ to own device buffers and streams.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import enum
 import os
 
@@ -26,10 +27,28 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import (AUTO_RESET, BF16, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1, ONLY_P2, ROLL, ROLLOUT_ROTATE, ROLLOUT_VR,  # noqa: F401
-                    WANT_INDEX, WEIGHTS_SLOT1, BgamdError)
+from ._capi import (AUTO_RESET, BF16, CUBE_HOLD_TURN0, CUBE_JACOBY, CUBE_ON, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1,  # noqa: F401
+                    ONLY_P2, ROLL, ROLLOUT_ROTATE, ROLLOUT_VR, WANT_INDEX, WEIGHTS_SLOT1, BgamdError)
 
-__all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "BgamdError", "set_seed", "pack_rows", "outcomes"]
+__all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "Cube", "BgamdError", "set_seed", "pack_rows", "outcomes"]
+
+
+@dataclasses.dataclass
+class Cube:
+    """The doubling cube of VecGame.rollout(cube=...) (include/bgamd.h, bgamd_env_rollout_cube).  Before a turn the side to roll, with
+    access to the cube and w its chance to win by the pre-roll evaluation, doubles iff double_at <= w <= too_good_at; the other side
+    passes iff w > pass_at.  The defaults are a plain money-play rule of thumb, no measured optimum.  max_cube: no double at or beyond
+    it.  jacoby: a trial whose cube was never turned in the trial counts as a single game.  hold_turn0: no decision before a trial's
+    turn 0 (the roller holds the cube this turn: the "no double" line of a cube action).  value / owner: the cube at the start, a
+    scalar or one entry per position (a power of two; 0 = the centre, 1 = PLAYER1 owns it, 2 = PLAYER2); None = 1, centred."""
+    double_at: float = 0.70
+    pass_at: float = 0.78
+    too_good_at: float = 1.0
+    max_cube: int = 64
+    jacoby: bool = False
+    hold_turn0: bool = False
+    value: object = None
+    owner: object = None
 
 ERR_MESSAGES = {                                   # cppsrc/game.cpp:585-642, in source order
     0: "", 1: "Invalid origin", 2: "Origin out of range", 3: "Destination out of range",
@@ -405,7 +424,7 @@ class VecGame:
 
     def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
                 per_trial=False, variance_reduction=False, outcomes=False, plies=1, top_k=4, margin=float("inf"), groups=None,
-                group_offset=0):
+                group_offset=0, cube=None):
         """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
         move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
         trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
@@ -423,7 +442,15 @@ class VecGame:
         groups (int sequence or tensor [P]): dice groups (bgamd_env_rollout_grouped) -- trial i of position p rolls the dice of game id
         (group_offset + groups[p]) * trials + i instead, so the positions of a group share their trials' dice; every output stays indexed
         by position, and position p's are those of the single-position call with position_offset = group_offset + groups[p].
-        rollout_paired() then reads the differences inside a group.  groups with a non-zero position_offset: ValueError."""
+        rollout_paired() then reads the differences inside a group.  groups with a non-zero position_offset: ValueError.
+        cube (a Cube, or a dict of its fields): the doubling cube on the same trials (bgamd_env_rollout_cube, set for this call and
+        switched off afterwards) -- also cubeful [P], cubeful_stderr [P] (float64, PLAYER1's cubeful money equity in points) and
+        cube_counts [P, 4] (int64: trials PLAYER1 passed, trials PLAYER2 passed, cube turns, trials that ended at max_cube), with
+        per_trial trial_cubeful [P, T] (float64), trial_cube [P, T] (int32, the final cube), trial_dropped [P, T] (int32, the turn of
+        the drop or -1).  The other outputs are the same as without it.  The cube decides on the luck pass's pre-roll means: cube
+        without variance_reduction is a ValueError."""
+        if cube is not None and not variance_reduction:
+            raise ValueError("rollout: the cube decides on the luck pass's pre-roll means; pass variance_reduction=True with cube")
         if groups is not None and int(position_offset) != 0:
             raise ValueError("rollout: groups set the dice ids; pass group_offset, not position_offset")
         if groups is None and int(group_offset) != 0:
@@ -432,7 +459,7 @@ class VecGame:
             _capi.check(self._lib.bgamd_env_rollout_policy(self._h, int(plies), int(top_k), float(margin)), "rollout_policy")
             try:
                 return self.rollout(states28, turn, trials, max_plies, rotate, seed, slot, position_offset, lanes, per_trial,
-                                    variance_reduction, outcomes, groups=groups, group_offset=group_offset)
+                                    variance_reduction, outcomes, groups=groups, group_offset=group_offset, cube=cube)
             finally:
                 _capi.check(self._lib.bgamd_env_rollout_policy(self._h, 1, 0, 0.0), "rollout_policy")
         st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
@@ -451,17 +478,29 @@ class VecGame:
             out["trial_value"] = self._buf((P, max(T, 0)), torch.float32)
             out["trial_turns"] = self._buf((P, max(T, 0)), torch.int32)
         flags = (ROLLOUT_ROTATE if rotate else 0) | (WEIGHTS_SLOT1 if slot else 0) | (ROLLOUT_VR if variance_reduction else 0)
-        if groups is None:
-            _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
-                                                    int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
-                                                    _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
-                                                    _ptr(out.get("trial_turns")), _stream()), "rollout")
-        else:
-            _capi.check(self._lib.bgamd_env_rollout_grouped(self._h, flags, _ptr(st), _ptr(t), _ptr(grp), P, int(group_offset), T,
-                                                            int(max_plies), int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]),
-                                                            _ptr(out["stderr"]), _ptr(out["turns"]), _ptr(out["truncated"]),
-                                                            _ptr(out.get("trial_value")), _ptr(out.get("trial_turns")), _stream()),
-                        "rollout_grouped")
+        if cube is not None:
+            c = cube if isinstance(cube, Cube) else Cube(**cube)
+            cv = None if c.value is None else self._dev(c.value, torch.int32, (P,))
+            co = None if c.owner is None else self._dev(c.owner, torch.int32, (P,))
+            _capi.check(self._lib.bgamd_env_rollout_cube(self._h, CUBE_ON | (CUBE_JACOBY if c.jacoby else 0) |
+                                                         (CUBE_HOLD_TURN0 if c.hold_turn0 else 0), float(c.double_at),
+                                                         float(c.pass_at), float(c.too_good_at), int(c.max_cube), _ptr(cv), _ptr(co)),
+                        "rollout_cube")
+        try:
+            if groups is None:
+                _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
+                                                        int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
+                                                        _ptr(out["turns"]), _ptr(out["truncated"]), _ptr(out.get("trial_value")),
+                                                        _ptr(out.get("trial_turns")), _stream()), "rollout")
+            else:
+                _capi.check(self._lib.bgamd_env_rollout_grouped(self._h, flags, _ptr(st), _ptr(t), _ptr(grp), P, int(group_offset), T,
+                                                                int(max_plies), int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]),
+                                                                _ptr(out["stderr"]), _ptr(out["turns"]), _ptr(out["truncated"]),
+                                                                _ptr(out.get("trial_value")), _ptr(out.get("trial_turns")), _stream()),
+                            "rollout_grouped")
+        finally:
+            if cube is not None:                           # (the setting is sticky in the C ABI; here it lasts for the call, like plies)
+                _capi.check(self._lib.bgamd_env_rollout_cube(self._h, 0, 0.0, 0.0, 0.0, 0, None, None), "rollout_cube")
         self._rollout_shape = (P, T)
         if variance_reduction:
             out["vr_mean"], out["vr_stderr"] = self._buf((P,), torch.float64), self._buf((P,), torch.float64)
@@ -471,7 +510,31 @@ class VecGame:
                                                             _ptr(out.get("trial_luck")), _stream()), "rollout_vr_read")
         if outcomes:
             out.update(self.rollout_outcomes_read(per_trial=per_trial))
+        if cube is not None:
+            out.update(self.rollout_cube_read(per_trial=per_trial))
         return out
+
+    def rollout_cube_read(self, per_trial=False):
+        """The last rollout's cube results (bgamd_env_rollout_cube_read; raises unless that rollout had cube=) -> dict: cubeful [P],
+        cubeful_stderr [P], cube_counts [P, 4], per_trial: trial_cubeful, trial_cube, trial_dropped [P, T] -- see rollout(cube=)."""
+        P, T = self._rollout_shape
+        out = {"cubeful": self._buf((P,), torch.float64), "cubeful_stderr": self._buf((P,), torch.float64),
+               "cube_counts": self._buf((P, 4), torch.int64)}
+        if per_trial:
+            out["trial_cubeful"] = self._buf((P, T), torch.float64)
+            out["trial_cube"] = self._buf((P, T), torch.int32)
+            out["trial_dropped"] = self._buf((P, T), torch.int32)
+        _capi.check(self._lib.bgamd_env_rollout_cube_read(self._h, _ptr(out["cubeful"]), _ptr(out["cubeful_stderr"]),
+                                                          _ptr(out["cube_counts"]), _ptr(out.get("trial_cubeful")),
+                                                          _ptr(out.get("trial_cube")), _ptr(out.get("trial_dropped")), _stream()),
+                    "rollout_cube_read")
+        return out
+
+    def rollout_cube_info(self):
+        """The last cubeful rollout's [lane-turns played, lane-turns played after the trial's drop] (bgamd_env_rollout_cube_info)."""
+        h = (C.c_int64 * 2)()
+        _capi.check(self._lib.bgamd_env_rollout_cube_info(self._h, h), "rollout_cube_info")
+        return list(h)
 
     def rollout_outcomes_read(self, per_trial=False):
         """The last rollout's games in points (bgamd_env_rollout_outcomes_read; raises before the first rollout) -> dict: counts [P, 6],
@@ -486,17 +549,18 @@ class VecGame:
                     "rollout_outcomes_read")
         return out
 
-    PAIRED_WHICH = {"value": 0, "vr": 1, "equity": 2}
+    PAIRED_WHICH = {"value": 0, "vr": 1, "equity": 2, "cubeful": 3}
 
     def rollout_paired(self, ref, which="value"):
         """Paired differences of the last rollout (bgamd_env_rollout_paired_read): for each position p and its reference ref[p] (an index
         into that call's positions), mean and standard error of the per-trial differences q_i(p) - q_i(ref[p]) -- q the trial's value
-        ("value"), its luck-adjusted value ("vr": the rollout must have had variance_reduction) or its equity in points ("equity").  Only
+        ("value"), its luck-adjusted value ("vr": the rollout must have had variance_reduction), its equity in points ("equity") or its cubeful equity ("cubeful": the rollout
+        must have had cube=).  Only
         positions of one dice group share dice: a reference in another group, or out of range, gives NaN for that p; after a rollout
         without groups every ref[p] != p does.  ref[p] = p gives 0.  -> (diff_mean [P], diff_stderr [P]), float64 device tensors;
         stream-ordered."""
         if which not in self.PAIRED_WHICH:
-            raise ValueError("rollout_paired: which is one of 'value', 'vr', 'equity'")
+            raise ValueError("rollout_paired: which is one of 'value', 'vr', 'equity', 'cubeful'")
         P, _ = self._rollout_shape
         r = torch.as_tensor(ref).to(torch.int64).reshape(-1)
         if r.shape[0] != P:

@@ -1,5 +1,6 @@
-"""Move analysis on top of the env: which of a turn's moves is best by rollout (include/bgamd.h, bgamd_env_rollout), and how much a
-player's moves lose against a 2-ply judge (bgamd_env_analyze_moves)."""
+"""Move analysis on top of the env: which of a turn's moves is best by rollout (include/bgamd.h, bgamd_env_rollout), how much a
+player's moves lose against a 2-ply judge (bgamd_env_analyze_moves), and the cube action of a position by cubeful rollout
+(bgamd_env_rollout_cube)."""
 from __future__ import annotations
 
 import math
@@ -134,6 +135,88 @@ def rollout_decisions(env, top_k=8, trials=1296, max_plies=0, seed=20240603, var
             d, se = float(dm[q]), float(ds[q])
             c.update(diff=d, diff_stderr=se, jsd=0.0 if d == 0.0 else (math.inf if se == 0.0 else abs(d) / se))
             out[g].append(c)
+    return out
+
+
+CUBE_ACTIONS = ("no double, take", "double, take", "double, pass", "too good, pass", "too good, take")
+
+
+def cube_decision(nd, dt, dp):
+    """GNU Backgammon's cube action table on three cubeful equities from the roller's side: nd (no double), dt (double / take), dp
+    (double / pass = the cube's value).  The opponent takes iff dt <= dp; the roller doubles iff the better of the opponent's answers
+    still beats nd.  -> one of CUBE_ACTIONS"""
+    if dt <= dp:                                           # the take is right
+        if dt > nd:
+            return "double, take"
+        return "too good, take" if nd > dp else "no double, take"
+    return "too good, pass" if nd > dp else "double, pass"
+
+
+def cube_action(env, states28, turn, cube_value=1, cube_owner=0, trials=1296, max_plies=0, plies=1, rollout_top_k=4,
+                rollout_margin=float("inf"), seed=20240603, group_offset=0, lanes=0, cube=None):
+    """Double or not, take or pass: the cube action of each position by ONE grouped cubeful rollout.
+
+    env: a VecGame with weights in slot 0 (its lanes are untouched).  states28 [P, 28] / turn [P]: the positions, `turn` to roll and
+    to decide.  cube_value / cube_owner (scalars or [P]): the cube as it stands, c and 0 = centre, 1 = PLAYER1, 2 = PLAYER2.
+    cube: the rule the trials handle the cube by afterwards (a backgammon_env.Cube or a dict of its fields; value, owner and hold_turn0
+    are set here; jacoby is refused -- the rule counts cube turns inside a trial, and the double under analysis is made before it).
+    Every position whose roller has access to the cube appears twice in the rollout, in the same dice group (its index, counted from
+    group_offset): as it stands with no decision before turn 0 ("no double": the roller holds the cube this turn, and the rule applies
+    from the opponent's turn on), and with cube 2 c owned by the opponent ("double / take").  `trials` rotated trials each, turn limit
+    max_plies (0 = to the end), played by the greedy step or, plies = 2, by the filtered 2-ply search (rollout_top_k, rollout_margin).
+
+    -> one dict per position, every equity in points from the ROLLER's side:
+         nd, nd_stderr    cubeful equity of not doubling;  dt, dt_stderr  of double / take;  dp = +c  of double / pass;
+         diff, diff_stderr, jsd   the paired dt - nd over the shared dice (VecGame.rollout_paired(which="cubeful")), its standard error,
+                          and |diff| / diff_stderr (0.0 where diff is 0, inf where only diff_stderr is);
+         cubeless, cubeless_stderr   the cubeless equity of the no-double copy's trials;  shares: win, win_gammon, win_backgammon,
+                          lose, lose_gammon, lose_backgammon as fractions of the trials (gammons include backgammons; truncated
+                          trials are in none);
+         action           one of CUBE_ACTIONS by cube_decision(nd, dt, dp).
+       A position whose roller has no access to the cube carries nd (and the cubeless fields) only, with action "no access"; a
+       position that is already over likewise, with action "game over"."""
+    from . import Cube
+    st = np.asarray(states28.cpu() if hasattr(states28, "cpu") else states28, dtype=np.int32).reshape(-1, 28)
+    P = st.shape[0]
+    tu = np.broadcast_to(np.asarray(turn.cpu() if hasattr(turn, "cpu") else turn, dtype=np.int64), (P,))
+    cv = np.broadcast_to(np.asarray(cube_value, dtype=np.int64), (P,))
+    co = np.broadcast_to(np.asarray(cube_owner, dtype=np.int64), (P,))
+    rule = cube if isinstance(cube, Cube) else Cube(**(cube or {}))
+    if rule.jacoby:
+        raise ValueError("cube_action: the Jacoby rule counts cube turns inside a trial; the double under analysis is made before it")
+    over = (st[:, 26] == 15) | (st[:, 27] == 15)
+    access = ((co == 0) | (co == tu + 1)) & ~over
+    nd_of = list(range(P))
+    dt_of = {}
+    rows, turns, values, owners, groups = list(range(P)), list(tu), list(cv), list(co), list(range(P))
+    for p in np.flatnonzero(access):
+        dt_of[int(p)] = len(rows)
+        rows.append(int(p)); turns.append(tu[p]); values.append(2 * cv[p]); owners.append(2 - tu[p]); groups.append(int(p))
+    rule = Cube(rule.double_at, rule.pass_at, rule.too_good_at, rule.max_cube, False, True, np.asarray(values), np.asarray(owners))
+    r = env.rollout(st[rows], np.asarray(turns), trials, max_plies=max_plies, rotate=True, seed=seed, lanes=lanes, variance_reduction=True,
+                    outcomes=True, plies=plies, top_k=rollout_top_k, margin=rollout_margin, groups=groups, group_offset=group_offset,
+                    cube=rule)
+    ref = [nd_of[g] for g in groups]                       # every copy against its position's no-double copy
+    dm, ds = (x.cpu().numpy() for x in env.rollout_paired(ref, "cubeful"))
+    h = {k: v.cpu().numpy() for k, v in r.items()}
+    T = float(int(trials))
+    out = []
+    for p in range(P):
+        sg = 1.0 if tu[p] == 0 else -1.0
+        cnt = h["counts"][p] if tu[p] == 0 else np.concatenate([h["counts"][p][3:], h["counts"][p][:3]])
+        e = {"nd": sg * float(h["cubeful"][p]), "nd_stderr": float(h["cubeful_stderr"][p]),
+             "cubeless": sg * float(h["equity"][p]), "cubeless_stderr": float(h["equity_stderr"][p]),
+             "shares": {"win": int(cnt[:3].sum()) / T, "win_gammon": int(cnt[1:3].sum()) / T, "win_backgammon": int(cnt[2]) / T,
+                        "lose": int(cnt[3:].sum()) / T, "lose_gammon": int(cnt[4:].sum()) / T, "lose_backgammon": int(cnt[5]) / T}}
+        if p in dt_of:
+            q = dt_of[p]
+            d, se = sg * float(dm[q]), float(ds[q])
+            e.update(dt=sg * float(h["cubeful"][q]), dt_stderr=float(h["cubeful_stderr"][q]), dp=float(cv[p]), diff=d, diff_stderr=se,
+                     jsd=0.0 if d == 0.0 else (math.inf if se == 0.0 else abs(d) / se))
+            e["action"] = cube_decision(e["nd"], e["dt"], e["dp"])
+        else:
+            e["action"] = "game over" if over[p] else "no access"
+        out.append(e)
     return out
 
 

@@ -22,6 +22,7 @@ constexpr uint32_t RO_TURN_LIMIT = 100000;           // M = 0: a trial still run
 enum { RO_NEXT = 0, RO_DONE = 1, RO_NTRUNC = 2, RO_ERR = 3, RO_CTRS = 4 };
 enum { ERRF_RO_LONG = 8, ERRF_RO_PLY = 16 };
 enum { ERRF_RO_GROUP = 256 };                        // intake word, beside ERRF_STATE: a bad group table (bg_rollout_groups.h)
+enum { ERRF_RO_CUBE = 512 };                         // intake word: a bad entry of the cube's start tables (bg_cube.h)
 
 struct RoView {
     long long N, T, M;                                // trials in all, per position, turn limit (0 = none)

@@ -48,6 +48,7 @@ constexpr bool EXPERIMENTAL_BUILD = false;
 #include "bg_movegen.h"
 #include "bg_staged.h"
 #include "bg_search3.h"
+#include "bg_cube.h"
 
 using namespace bg;
 
@@ -810,7 +811,20 @@ struct RolloutState {
     int32_t *group = nullptr;              // [cap_group] the group table of the last bgamd_env_rollout_grouped (bgamd_env_rollout_paired_read)
     long long cap_group = 0;
     bool grouped = false;                  // the last rollout had a group table (false: the identity, `group` is not read)
+    // the doubling cube (bgamd_env_rollout_cube, bg_cube.h): ctrial [cap_ctrials] the trials' records, ceq [cap_ctrials] their cubeful
+    // equities (left by the reduce launch that ends a cubeful rollout: bgamd_env_rollout_paired_read's which = 3), cstart [2 cap_cstart]
+    // the env's copy of the start tables, cctr [2] the lane-turn counters
+    cube::Trial *ctrial = nullptr;
+    double *ceq = nullptr;
+    uint32_t *cstart = nullptr;
+    unsigned long long *cctr = nullptr;
+    long long cap_ctrials = 0, cap_cstart = 0;
+    long long cube_P = 0, cube_T = 0;      // P, T of the last rollout if the cube was on (0: bgamd_env_rollout_cube_read refuses)
+    cube::Rule cube_rule{};                // ... and the rule it was played under
+    int64_t cube_info[2] = {0, 0};         // bgamd_env_rollout_cube_info
 };
+static_assert(cube::LANE_FINISHED == META_FINISHED && cube::LANE_NONE == RO_NONE && cube::WORD_TRUNC == RO_TRUNC &&
+              cube::WORD_PTS_SHIFT == RO_PTS_SHIFT && cube::ROLLS == SRCH_ROLLS, "bg_cube.h restates these");
 
 // pre-roll evaluation (bgamd_env_evaluate_preroll, bg_vr.h)
 struct PrerollState {
@@ -867,6 +881,10 @@ struct bgamd_env {
     SearchLog slog;                        // set: search steps log into it, every other step is refused (bgamd_env_set_search_log)
     int ro_plies = 1, ro_top_k = 0;        // bgamd_env_rollout_policy: who plays the trials' turns (1 = the greedy step)
     float ro_margin = 0.0f;
+    // bgamd_env_rollout_cube: the sticky cube setting (flags 0 = off) and the caller's start tables, read by the next rollout's intake
+    int cube_flags = 0;
+    cube::Rule cube_rule{0.70, 0.78, 1.0, 64u, 0, 0};
+    const int32_t *cube_value = nullptr, *cube_owner = nullptr;
     AnalysisState ana;
     RolloutState ro;
     PrerollState pre;
@@ -2271,10 +2289,14 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
 {
     if (env) env->ro.vr_P = 0;                         // (bgamd_env_rollout_vr_read: only after a call that had the flag)
     if (env) env->ro.out_P = 0;                        // (bgamd_env_rollout_outcomes_read: only after a call that succeeded)
+    if (env) env->ro.cube_P = 0;                       // (bgamd_env_rollout_cube_read: only after a call that had the cube on)
     if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
     if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1 | BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
     if (n_positions >= (1ll << 31) || trials >= (1ll << 31) || n_positions * trials >= (1ll << 31) || lanes > (1ll << 30))
         return BGAMD_E_INVALID;
+    // the cube rides on the luck pass's pre-roll means: without them there is nothing to decide on
+    const bool cube_on = (env->cube_flags & BGAMD_CUBE_ON) != 0;
+    if (cube_on && !(flags & BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
     const int slot = (flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
     if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
@@ -2300,6 +2322,11 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
                (rc = mem.grow(P, ro.cap_vpos, {BG_BUF(ro.f0, 4 * SRCH_ROLLS), BG_BUF(ro.m0, 8)}))))
         return rc;
     if (d_group && (rc = mem.grow(P, ro.cap_group, {BG_BUF(ro.group, 4)}))) return rc;
+    if (cube_on && ((rc = mem.grow(N, ro.cap_ctrials, {BG_BUF(ro.ctrial, sizeof(cube::Trial)), BG_BUF(ro.ceq, 8)})) ||
+                    (rc = mem.grow(P, ro.cap_cstart, {BG_BUF(ro.cstart, 2 * 4)})) ||
+                    (!ro.cctr && (rc = mem.alloc(BG_BUF(ro.cctr, cube::CTR_WORDS * 8))))))
+        return rc;
+    const cube::Rule cube_rule = env->cube_rule;
     if (!ro.host && (rc = mem.alloc_pinned(BG_BUF(ro.host, 8 * 8)))) return rc;        // the pinned words and the two events: first use
     for (hipEvent_t &e : ro.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     unsigned long long *h = ro.host, *ctr = env->a_ctr;
@@ -2310,8 +2337,9 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
     // ... and, in the same pass, a bad group table: the env's copy is written, checked, and read by nothing before the synchronise
     unsigned long long intake = 0;
     if (d_group) hipLaunchKernelGGL(ro_group_intake_kernel<128>, grid1(P, 128), dim3(128), 0, s, d_group, P, T, ro.group, &env->a_ctr[A_INTAKE]);
+    if (cube_on) cube::intake(s, P, env->cube_value, env->cube_owner, ro.cstart, &env->a_ctr[A_INTAKE], (unsigned long long)ERRF_RO_CUBE);
     rc = intake_positions(env, d_states28, d_turn, P, ro.pos, s, &intake);
-    if (intake & ERRF_RO_GROUP) return BGAMD_E_INVALID;
+    if (intake & (ERRF_RO_GROUP | ERRF_RO_CUBE)) return BGAMD_E_INVALID;
     if (rc) return rc;
 
     // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1.
@@ -2364,12 +2392,18 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
         }
         hipLaunchKernelGGL(ro_vr_init_kernel, dim3((unsigned)(sc->n_cu * 4)), dim3(RO_NT), 0, s, r, (const float *)ro.f0,
                            (const double *)ro.m0, ro.tluck);
+        // the cube: every trial's record at its start, with the decision before a rotated turn 0 on the position's own mean
+        if (cube_on) {
+            HIPCHK(hipMemsetAsync(ro.cctr, 0, cube::CTR_WORDS * 8, s));
+            cube::init(s, N, T, rotate ? 1 : 0, ro.pos, ro.cstart, P, ro.m0, cube_rule, ro.ctrial);
+        }
         HIPCHK(hipGetLastError());
     }
     // (the roots of the turn at hand are in place: the board, side to move and dice of every live trial lane)
     auto vr_turn = [&]() -> int {
         if (const int e = preroll_pass(env, slot, L, nullptr, &sc->v, ro.vf, s)) return e;
         hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)ro.lane, (const float *)ro.vf, ro.tluck);
+        if (cube_on) cube::turn(s, L, sc->v.meta, sc->v.ply, ro.lane, ro.vf, cube_rule, ro.ctrial, ro.cctr);
         return BGAMD_OK;
     };
 
@@ -2452,8 +2486,18 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
 
     hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)P), dim3(64), 0, s, (long long)T, (const float *)ro.tval,
                        (const uint32_t *)ro.tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
+    // the cube: every trial's cubeful equity into the env's buffer (the paired read's which = 3); the two lane-turn counters
+    unsigned long long h_cube[cube::CTR_WORDS] = {0ull, 0ull};
+    if (cube_on) {
+        cube::reduce(s, P, T, ro.tval, ro.tturns, ro.ctrial, cube_rule, ro.ceq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        HIPCHK(hipMemcpyAsync(h_cube, ro.cctr, sizeof h_cube, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
+    if (cube_on) {
+        ro.cube_P = P; ro.cube_T = T; ro.cube_rule = cube_rule;
+        ro.cube_info[0] = (int64_t)h_cube[cube::CTR_TURNS]; ro.cube_info[1] = (int64_t)h_cube[cube::CTR_AFTER_DROP];
+    }
     if (vr) { ro.vr_P = P; ro.vr_T = T; }
     ro.out_P = P; ro.out_T = T;
     ro.grouped = d_group != nullptr;
@@ -2463,9 +2507,16 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
 int bgamd_env_rollout_paired_read(bgamd_env *env, const int32_t *d_ref, int which, double *d_diff_mean, double *d_diff_stderr, void *stream)
 {
     ENV_GUARD(env);
-    if (env->ro.out_P < 1 || !d_ref || which < 0 || which > 2) return BGAMD_E_INVALID;
+    if (env->ro.out_P < 1 || !d_ref || which < 0 || which > 3) return BGAMD_E_INVALID;
     if (which == 1 && env->ro.vr_P < 1) return BGAMD_E_INVALID;
     const RolloutState &ro = env->ro;
+    if (which == 3) {                                  // the cubeful equity: the buffer the cubeful rollout's reduce launch left (bg_cube.h)
+        if (ro.cube_P < 1) return BGAMD_E_INVALID;
+        cube::paired((hipStream_t)stream, ro.cube_P, ro.cube_T, d_ref, ro.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr,
+                     ro.ceq, d_diff_mean, d_diff_stderr);
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    }
     hipLaunchKernelGGL(ro_pair_reduce_kernel<64>, dim3((unsigned)ro.out_P), dim3(64), 0, (hipStream_t)stream, (long long)ro.out_P,
                        (long long)ro.out_T, which, d_ref, ro.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr,
                        (const float *)ro.tval, (const uint32_t *)ro.tturns, (const double *)ro.tluck, d_diff_mean, d_diff_stderr);
@@ -2477,6 +2528,45 @@ int bgamd_env_rollout_policy(bgamd_env *env, int plies, int top_k, float margin)
 {
     if (!env || (plies != 1 && plies != 2) || top_k < 0 || !(margin >= 0.0f)) return BGAMD_E_INVALID;
     env->ro_plies = plies; env->ro_top_k = top_k; env->ro_margin = margin;
+    return BGAMD_OK;
+}
+
+// ---- the doubling cube on the rollout's trials (bg_cube.h) -----------------------------------------------------------------------------
+int bgamd_env_rollout_cube(bgamd_env *env, int cube_flags, double double_at, double pass_at, double too_good_at, int64_t max_cube,
+                           const int32_t *d_cube_value, const int32_t *d_cube_owner)
+{
+    if (!env || (cube_flags & ~(BGAMD_CUBE_ON | BGAMD_CUBE_JACOBY | BGAMD_CUBE_HOLD_TURN0))) return BGAMD_E_INVALID;
+    if (!(cube_flags & BGAMD_CUBE_ON)) {               // off (another flag alone is nothing): the rollouts launch what they did before
+        if (cube_flags) return BGAMD_E_INVALID;
+        env->cube_flags = 0; env->cube_value = nullptr; env->cube_owner = nullptr;
+        return BGAMD_OK;
+    }
+    auto in01 = [](double x) { return x >= 0.0 && x <= 1.0; };     // (false for a NaN)
+    if (!in01(double_at) || !in01(pass_at) || !in01(too_good_at) || double_at > too_good_at) return BGAMD_E_INVALID;
+    if (max_cube < 1 || max_cube > (1ll << 30) || (max_cube & (max_cube - 1))) return BGAMD_E_INVALID;
+    env->cube_flags = cube_flags;
+    env->cube_rule = cube::Rule{double_at, pass_at, too_good_at, (uint32_t)max_cube, (cube_flags & BGAMD_CUBE_JACOBY) ? 1 : 0,
+                                (cube_flags & BGAMD_CUBE_HOLD_TURN0) ? 1 : 0};
+    env->cube_value = d_cube_value; env->cube_owner = d_cube_owner;
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_cube_read(bgamd_env *env, double *d_cubeful, double *d_cubeful_stderr, int64_t *d_counts, double *d_trial_cubeful,
+                                int32_t *d_trial_cube, int32_t *d_trial_dropped, void *stream)
+{
+    ENV_GUARD(env);
+    const RolloutState &ro = env->ro;
+    if (ro.cube_P < 1) return BGAMD_E_INVALID;
+    cube::reduce((hipStream_t)stream, ro.cube_P, ro.cube_T, ro.tval, ro.tturns, ro.ctrial, ro.cube_rule, ro.ceq, d_cubeful, d_cubeful_stderr,
+                 d_counts, d_trial_cubeful, d_trial_cube, d_trial_dropped);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_cube_info(bgamd_env *env, int64_t h_out[2])
+{
+    if (!env || !h_out) return BGAMD_E_INVALID;
+    h_out[0] = env->ro.cube_info[0]; h_out[1] = env->ro.cube_info[1];
     return BGAMD_OK;
 }
 

@@ -477,7 +477,8 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
                               float *d_trial_value, int32_t *d_trial_turns, void *stream);
 /* Paired differences of the last rollout of either kind (P and T of that call; BGAMD_E_INVALID before the first or after one that failed).
  * `which` selects the per-trial quantity q: 0 the value x_i; 1 the luck-adjusted y_i = (double) x_i - L_i (BGAMD_E_INVALID unless that
- * rollout had BGAMD_ROLLOUT_VR); 2 the equity e_i in points as bgamd_env_rollout_outcomes_read defines it.  Other values: BGAMD_E_INVALID.
+ * rollout had BGAMD_ROLLOUT_VR); 2 the equity e_i in points as bgamd_env_rollout_outcomes_read defines it; 3 the cubeful
+ * equity of bgamd_env_rollout_cube_read (BGAMD_E_INVALID unless that rollout ran with the cube on).  Other values: BGAMD_E_INVALID.
  * For each position p with its reference r = d_ref[p], in fp64:
  *   d_i = q_i(p) - q_i(r);  d_diff_mean[p] = (1/T) sum d_i;  d_diff_stderr[p] = sqrt(sum (d_i - diff_mean)^2 / (T (T - 1))), 0 for T = 1,
  * reduced in the fixed order of the plain statistics (one wave per position, lane k takes trials k, k + 64, ..., then the same butterfly).
@@ -567,6 +568,62 @@ int bgamd_env_outcomes(bgamd_env *env, int32_t *d_points, void *stream);
  * that make up a turn's luck come from a one-output net that estimates P(PLAYER1 wins) and knows nothing of gammons. */
 int bgamd_env_rollout_outcomes_read(bgamd_env *env, int64_t *d_counts, double *d_equity, double *d_equity_stderr,
                                     int8_t *d_trial_points, void *stream);
+
+/* ---- the doubling cube on the rollout's trials: cubeful money equity ------------------------------------------------------------------
+ * The net knows wins only, so the cube never changes which checker move is played: a cubeful rollout is an OVERLAY on the trials as
+ * bgamd_env_rollout plays them.  Every trial carries a record -- the cube value c (a power of two), its owner o (0 the centre, 1 PLAYER1,
+ * 2 PLAYER2), the turn index of a drop (or -1) with the side that passed, and how often the cube was turned in the trial -- which is
+ * advanced before every turn from the pre-roll mean the luck pass (BGAMD_ROLLOUT_VR) computes anyway.  The cubeless and the cubeful
+ * results come from the same trials, as GNU Backgammon reports them.
+ * THE RULE.  A trial of position p starts with c = d_cube_value[p] and o = d_cube_owner[p] (NULL tables: 1, in the centre).  Before turn
+ * k of the trial the board is s_k and m_k is to roll -- turn 0 and a rotated turn 0 included, the latter on the position's own pre-roll
+ * mean, evaluated once per call like the turn-0 luck.  A cube decision is made iff the trial has not been dropped, the position is not
+ * over, c < max_cube, and o is the centre or m_k.  Then, in fp64:
+ *   w = mean(s_k) for PLAYER1 to roll, 1.0 - mean(s_k) for PLAYER2 (one subtraction); mean is bit-identical to what
+ *       bgamd_env_evaluate_preroll returns for (s_k, m_k) with the rollout's weight slot;
+ *   m_k doubles iff double_at <= w && w <= too_good_at;
+ *   the opponent then passes iff w > pass_at: the trial is dropped at turn k and its cubeful result is c, the value BEFORE the double,
+ *       won by m_k; else it takes: c <- 2 c, o <- the opponent, one more cube turn.
+ * A pass (no legal move) is a turn like any other and the cube is offered before it.  The trial keeps being played after a drop (its
+ * lane is not freed: bgamd_env_rollout_cube_info reports what that costs).
+ * Cubeful equity of a trial from PLAYER1's side, fp64: dropped: +c if PLAYER2 passed, -c if PLAYER1 did (c at the drop); finished on the
+ * board: c_final * points, points = +-1, +-2, +-3 as bgamd_env_rollout_outcomes_read records them; with BGAMD_CUBE_JACOBY a trial whose
+ * cube was never turned IN THE TRIAL counts as a single game, c_final * (+-1), whatever cube it started with; truncated at max_plies:
+ * c * (2.0 * (double) x_i - 1.0).  No further cube leverage is credited at the horizon (no Janowski-style live-cube equity): out of scope.
+ * The defaults suggested for the thresholds -- double_at 0.70, pass_at 0.78, too_good_at 1.0 (never too good: w is a win probability
+ * and knows no gammons), max_cube 64 -- are a plain money-play rule of thumb and NO measured optimum.
+ *
+ * BGAMD_CUBE_HOLD_TURN0: no decision is made before turn 0 of a trial (rotated or not); from turn 1 on the rule is as above.  It is what
+ * "no double" means when a cube action is analysed: the roller holds the cube this turn, and both sides handle it by the rule afterwards.
+ *
+ * bgamd_env_rollout_cube is a sticky setting like bgamd_env_rollout_policy.  cube_flags: 0 switches the cube off (the default: the
+ * rollouts' launches and results are what they are on an env that never called this; the other arguments are ignored), or BGAMD_CUBE_ON,
+ * alone or with BGAMD_CUBE_JACOBY and / or BGAMD_CUBE_HOLD_TURN0.  d_cube_value / d_cube_owner are DEVICE pointers (either may be NULL), read by the next rollout's
+ * intake pass; their length is that call's P, and they must stay valid until that call.  Errors (BGAMD_E_INVALID, the setting
+ * unchanged): other flags, a flag without BGAMD_CUBE_ON, a NaN threshold, a threshold outside [0, 1], double_at > too_good_at,
+ * max_cube not a power of two in 1 .. 2^30.
+ * While the cube is on: a rollout call without BGAMD_ROLLOUT_VR returns BGAMD_E_INVALID before anything is played; a table entry that is
+ * no power of two in 1 .. 2^30, or an owner outside 0 .. 2, is refused (BGAMD_E_INVALID) in the pass that refuses bad states.  The plain
+ * outputs, bgamd_env_rollout_info, bgamd_env_rollout_vr_read, bgamd_env_rollout_outcomes_read and bgamd_env_rollout_paired_read with
+ * which 0 .. 2 are bit for bit what the same call without the cube returns.
+ * Out of scope: the cube in live envs, self-play and the arena; match play; cube-aware checker play; freeing a lane at a drop; cubeful
+ * rollouts without the luck pass. */
+enum { BGAMD_CUBE_ON = 1, BGAMD_CUBE_JACOBY = 2, BGAMD_CUBE_HOLD_TURN0 = 4 };
+int bgamd_env_rollout_cube(bgamd_env *env, int cube_flags, double double_at, double pass_at, double too_good_at, int64_t max_cube,
+                           const int32_t *d_cube_value /*[P]*/, const int32_t *d_cube_owner /*[P]*/);
+/* The cube results of the last rollout, which must have run with the cube on (else BGAMD_E_INVALID); P and T of that call.  Any pointer
+ * may be NULL.  d_cubeful[P], d_cubeful_stderr[P] (fp64): mean and standard error of the per-trial cubeful equity, reduced in the fixed
+ * order of the plain statistics (one wave per position, lane k takes trials k, k + 64, ..., then the same butterfly), every sum a chain
+ * of rounded fp64 additions.  d_counts[P][4] (int64): trials that PLAYER1 passed, trials that PLAYER2 passed, cube turns in all, trials
+ * whose final cube is >= max_cube.  d_trial_cubeful[P][T] (fp64), d_trial_cube[P][T] (int32, the final cube), d_trial_dropped[P][T]
+ * (int32, the turn of the drop or -1).  Like every rollout result bit for bit independent of `lanes`, of the call order and of
+ * position_offset / group_offset splits.  Stream-ordered. */
+int bgamd_env_rollout_cube_read(bgamd_env *env, double *d_cubeful, double *d_cubeful_stderr, int64_t *d_counts, double *d_trial_cubeful,
+                                int32_t *d_trial_cube, int32_t *d_trial_dropped, void *stream);
+/* host values of the last cubeful rollout: h_out = [turns played on the trial env's lanes (a rotated turn 0 is not: it is played once per
+ * ordered pair), those of them played after the trial's drop, the turn the drop is made before included].  h_out[1] / h_out[0] is the
+ * share of the rollout's work that freeing a lane at a drop would save. */
+int bgamd_env_rollout_cube_info(bgamd_env *env, int64_t h_out[2]);
 
 /* (slot 8 below counts the 32-row x 2-feature MFMA steps of the dense f32 net, or the W1 columns added by the
  * incremental one) */

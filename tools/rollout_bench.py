@@ -9,6 +9,10 @@ each: the plain call and the VR call of the same trials, ms per call, the VR pas
 VR call adds), the per-position variance ratio (stderr / vr_stderr)^2 (median, min, max, pooled) and effective trials/s (trials/s x the
 median ratio; 1 for the plain call).
 
+--cube (with --vr): beside every VR call the same call with the doubling cube on (bgamd_env_rollout_cube, the header's default rule, the
+cube results read inside the timed region): ms per call with and without the cube, their ratio, and the share of lane-turns played
+after the trial's drop (bgamd_env_rollout_cube_info) -- what not freeing a lane at a drop costs.
+
 --outcomes: the same run with the games read in points after every call (bgamd_env_rollout_outcomes_read, inside the timed region):
 every record also carries the six shares (PLAYER1 single game / gammon / backgammon, PLAYER2 the same) over the finished trials of all
 positions and the mean equity of the positions in points.
@@ -75,6 +79,7 @@ def main():
     ap.add_argument("--regions", type=int, default=3)
     ap.add_argument("--vr", action="store_true", help="luck-adjusted rollouts against plain ones")
     ap.add_argument("--vr-trials", type=int, default=2592)
+    ap.add_argument("--cube", action="store_true", help="--vr: also the same VR calls with the doubling cube on")
     ap.add_argument("--outcomes", action="store_true", help="also read gammons / backgammons and the equity in points")
     ap.add_argument("--plies", type=int, default=1, choices=(1, 2), help="who plays the trials: 1 = the greedy step, 2 = the filtered 2-ply search")
     ap.add_argument("--top-k", type=int, default=5, help="--plies 2: the search's top_k")
@@ -86,6 +91,8 @@ def main():
     a = ap.parse_args()
     global POLICY
     POLICY = dict(plies=2, top_k=a.top_k, margin=a.margin) if a.plies == 2 else {}
+    if a.cube and not a.vr:
+        ap.error("--cube rides on the luck pass: give it with --vr")
     if a.vr and a.outcomes:
         ap.error("--outcomes reads the plain run's games; it is not combined with --vr")
     import backgammon_env as bg
@@ -205,13 +212,15 @@ def _groups(bg, w, a):
     print(json.dumps({"rollout_groups_bench": rec}))
 
 
-def _timed(env, st, tu, trials, M, lanes, regions, vr):
-    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, **POLICY)      # warm-up
+def _timed(env, st, tu, trials, M, lanes, regions, vr, cube=None):
+    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, cube=cube, **POLICY)      # warm-up
     ms = []
     for _ in range(regions):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, **POLICY)
+        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, cube=cube, **POLICY)
+        if cube is not None:
+            torch.cuda.synchronize()                               # (the cube read is stream-ordered after the call)
         ms.append((time.perf_counter() - t0) * 1e3)                # (the call synchronises; vr_read is stream-ordered after it)
     torch.cuda.synchronize()
     return statistics.median(ms), r, ms
@@ -240,6 +249,17 @@ def _vr(env, st, tu, a, greedy_sps):
                "plain_effective_trials_per_s": round(n_trials / ms_p * 1e3),
                "vr_effective_trials_per_s": round(n_trials / ms_v * 1e3 * med),
                "mean_turns": round(turns / n_trials, 2), "vr_regions_ms": [round(x, 2) for x in regions]}
+        if a.cube:
+            import backgammon_env as bg
+            ms_c, rc, cregions = _timed(env, st, tu, a.vr_trials, M, a.lanes, a.regions, True, cube=bg.Cube())
+            played, after = env.rollout_cube_info()
+            cc = rc["cube_counts"].sum(0).cpu().numpy()
+            rec.update({"cube_ms": round(ms_c, 2), "cube_over_vr": round(ms_c / ms_v, 4), "cube_regions_ms": [round(x, 2) for x in cregions],
+                        "cube_lane_turns": played, "cube_lane_turns_after_drop": after,
+                        "cube_share_after_drop": round(after / max(played, 1), 4),
+                        "cube_dropped_share": round(float(cc[0] + cc[1]) / n_trials, 4), "cube_turns_per_trial": round(float(cc[2]) / n_trials, 4),
+                        "cubeful_mean": round(float(rc["cubeful"].mean()), 5), "cubeless_same_trials_unchanged": bool(
+                            torch.equal(rc["mean"], rv["mean"]) and torch.equal(rc["vr_mean"], rv["vr_mean"]))})
         print(json.dumps(rec), flush=True)
         out.append(rec)
     print(json.dumps({"rollout_vr_bench": out}))
