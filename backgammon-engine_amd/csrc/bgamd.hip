@@ -45,6 +45,7 @@ constexpr bool EXPERIMENTAL_BUILD = false;
 #include "bg_fit.h"
 #include "bg_schedule.h"
 #include "bg_step_plan.h"
+#include "bg_rollout_plan.h"
 #include "bg_movegen.h"
 #include "bg_staged.h"
 #include "bg_search3.h"
@@ -794,6 +795,17 @@ struct AnalysisState {
     bool ready = false;                    // an analysis has run and nothing has failed since (bgamd_env_analysis_read)
 };
 
+// What the env remembers of its last rollout call: the read calls (bgamd_env_rollout_*_read) test it.  One assignment clears `ok` when a
+// call begins, one fills the record when it has succeeded; info / cube_info keep the numbers of the last call that did (with the cube).
+struct RolloutResult {
+    bool ok = false;                       // the last call succeeded; false: none yet, or it failed -- every read refuses, and only the infos below mean anything
+    bool vr = false, cube = false, grouped = false;    // it had BGAMD_ROLLOUT_VR / the cube on / a group table (false: RolloutState::group is not read)
+    long long P = 0, T = 0;
+    cube::Rule cube_rule{};                // cube: the rule it was played under
+    int64_t info[4] = {0, 0, 0, 0};        // bgamd_env_rollout_info
+    int64_t cube_info[2] = {0, 0};         // bgamd_env_rollout_cube_info
+};
+
 // Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h), and what the luck-adjusted ones add (bg_vr.h)
 struct RolloutState {
     uint4 *pos = nullptr, *fan = nullptr, *trows = nullptr;        // [cap_pos], [cap_fan], [cap_lanes]
@@ -802,15 +814,11 @@ struct RolloutState {
     long long cap_pos = 0, cap_fan = 0, cap_trials = 0, cap_lanes = 0;
     unsigned long long *host = nullptr;    // pinned, [2][4] (done, truncated, rollout error bits, env error bits) of the last two reads
     hipEvent_t ev[2] = {nullptr, nullptr}; // ... and the event behind each of the two
-    int64_t info[4] = {0, 0, 0, 0};        // bgamd_env_rollout_info
     double *tluck = nullptr, *m0 = nullptr;                        // tluck [P T] luck totals, m0 [P] / f0 [P][21]: turn 0 (rotation)
     float *vf = nullptr, *f0 = nullptr;                            // vf [L][21]: the trial lanes' f of the turn at hand
     long long cap_vtrials = 0, cap_vlanes = 0, cap_vpos = 0;
-    long long vr_P = 0, vr_T = 0;          // P, T of the last rollout if it had BGAMD_ROLLOUT_VR (0: bgamd_env_rollout_vr_read refuses)
-    long long out_P = 0, out_T = 0;        // P, T of the last rollout (0: none yet, or it failed: bgamd_env_rollout_outcomes_read refuses)
     int32_t *group = nullptr;              // [cap_group] the group table of the last bgamd_env_rollout_grouped (bgamd_env_rollout_paired_read)
     long long cap_group = 0;
-    bool grouped = false;                  // the last rollout had a group table (false: the identity, `group` is not read)
     // the doubling cube (bgamd_env_rollout_cube, bg_cube.h): ctrial [cap_ctrials] the trials' records, ceq [cap_ctrials] their cubeful
     // equities (left by the reduce launch that ends a cubeful rollout: bgamd_env_rollout_paired_read's which = 3), cstart [2 cap_cstart]
     // the env's copy of the start tables, cctr [2] the lane-turn counters
@@ -819,12 +827,10 @@ struct RolloutState {
     uint32_t *cstart = nullptr;
     unsigned long long *cctr = nullptr;
     long long cap_ctrials = 0, cap_cstart = 0;
-    long long cube_P = 0, cube_T = 0;      // P, T of the last rollout if the cube was on (0: bgamd_env_rollout_cube_read refuses)
-    cube::Rule cube_rule{};                // ... and the rule it was played under
-    int64_t cube_info[2] = {0, 0};         // bgamd_env_rollout_cube_info
+    RolloutResult last;
 };
 static_assert(cube::LANE_FINISHED == META_FINISHED && cube::LANE_NONE == RO_NONE && cube::WORD_TRUNC == RO_TRUNC &&
-              cube::WORD_PTS_SHIFT == RO_PTS_SHIFT && cube::ROLLS == SRCH_ROLLS, "bg_cube.h restates these");
+              cube::WORD_PTS_SHIFT == RO_PTS_SHIFT && cube::ROLLS == SRCH_ROLLS && ROLLOUT_ROLLS == SRCH_ROLLS, "bg_cube.h and bg_rollout_plan.h restate these");
 
 // pre-roll evaluation (bgamd_env_evaluate_preroll, bg_vr.h)
 struct PrerollState {
@@ -1822,11 +1828,7 @@ int bgamd_env_sample_info(bgamd_env *env, int64_t h_out[2])
 }
 
 // ---- what the 2-ply search, the pre-roll evaluation and the rollouts share --------------------------------------------------------
-// Virtual lanes per scoring pass: the search's scratch env has at most this many lanes (a 131 072-lane env: ~3.4 GB).  Every virtual
-// lane is scored on its own, so no result depends on it.
-constexpr long long SEARCH_CHUNK = 131072;
-// the lanes env->scratch needs for n_virtual virtual lanes: rounded up to 256, at most SEARCH_CHUNK
-static long long search_lanes(long long n_virtual) { return n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK; }
+// (SEARCH_CHUNK, the virtual lanes per scoring pass, and search_lanes: bg_rollout_plan.h)
 
 // *which (env->scratch or env->rscratch) ready to use: an env on env's device with want_lanes lanes -- exactly that many (exact), else
 // at least that many -- created, or after a wait for s re-created, when the one at hand does not do.  Leaves env's device current and
@@ -2224,10 +2226,11 @@ static int preroll_pass(bgamd_env *env, int slot, long long n, const uint4 *rows
     return score_virtual_lanes(env, slot, n * SRCH_ROLLS, fanout, f, s);
 }
 
-// the search's scratch env for n positions x 21 rolls, its error bits cleared: what preroll_pass scores on, preroll_errors reads
-static int preroll_begin(bgamd_env *env, long long n, hipStream_t s)
+// the search's scratch env with `lanes` lanes (search_lanes of positions x 21 rolls), its error bits cleared: what preroll_pass scores on,
+// preroll_errors reads
+static int preroll_begin(bgamd_env *env, long long lanes, hipStream_t s)
 {
-    if (int rc = scratch_env(env, &env->scratch, search_lanes(n * SRCH_ROLLS), false, 0, s)) return rc;
+    if (int rc = scratch_env(env, &env->scratch, lanes, false, 0, s)) return rc;
     HIPCHK(hipMemsetAsync(&env->scratch->v.counters[C_ERR], 0, 8, s));
     return BGAMD_OK;
 }
@@ -2257,7 +2260,7 @@ int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_state
     HIPCHK(hipMemsetAsync(&env->a_ctr[A_INTAKE], 0, 8, s));
     if ((rc = intake_positions(env, d_states28, d_turn, n, pre.rows, s))) return rc;
 
-    if ((rc = preroll_begin(env, n, s)) || (rc = preroll_pass(env, slot, n, pre.rows, nullptr, pre.f, s))) return rc;
+    if ((rc = preroll_begin(env, search_lanes(n * SRCH_ROLLS), s)) || (rc = preroll_pass(env, slot, n, pre.rows, nullptr, pre.f, s))) return rc;
     hipLaunchKernelGGL(pre_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)n, (const uint4 *)pre.rows, pre.f,
                        d_roll_values, d_mean);
     HIPCHK(hipGetLastError());
@@ -2265,11 +2268,207 @@ int bgamd_env_evaluate_preroll(bgamd_env *env, int flags, const int32_t *d_state
 }
 
 // ---- Monte Carlo rollouts (bg_rollout.h) -----------------------------------------------------------------------------------
-// Default lanes of the scratch env that plays the trials (a 65 536-lane env: ~1.7 GB); fewer when the call has fewer trials.
-constexpr long long ROLLOUT_LANES = 65536;
-// Turns per run between two refill points (M > 0: the largest divisor of the turns a trial has left at its start not above it).  A trial
-// that ends inside a run leaves its lane idle for the rest of the run: R / 2 turns per trial on average, against ~83 per game.
-constexpr int ROLLOUT_RUN = 8;
+namespace {
+// One call of bgamd_env_rollout_grouped after rollout_plan has decided it (bg_rollout_plan.h, plain C++, checked without a GPU: refusal,
+// lanes, run length, read-back period, buffer sizes): what the call kept in locals, and its schedule in the entry point's order
+struct RolloutCall {
+    bgamd_env *env;
+    const RolloutPlan &p;
+    hipStream_t s;
+    RolloutState &ro;                      // env->ro
+    bgamd_env *sc = nullptr;               // the trial env: env->rscratch, exactly p.L lanes
+    RoView r{};
+    long long steps = 0;                   // env steps issued on the trial env (bgamd_env_rollout_info [1])
+
+    // the scratch env (exactly L lanes) and the buffers of this call: one pass over the plan's needs (a need of 0 grows nothing)
+    int buffers()
+    {
+        DevMem &mem = env->mem;
+        const RolloutNeeds &n = p.needs;
+        int rc;
+        if ((rc = scratch_env(env, &env->rscratch, p.L, true, 1, s))) return rc;
+        sc = env->rscratch;
+        if ((rc = mem.grow(n.pos, ro.cap_pos, {BG_BUF(ro.pos, 32)})) ||
+            (rc = mem.grow(n.fan, ro.cap_fan, {BG_BUF(ro.fan, 32), BG_BUF(ro.fval, 4)})) ||
+            (rc = mem.grow(n.trials, ro.cap_trials, {BG_BUF(ro.tval, 4), BG_BUF(ro.tturns, 4)})) ||
+            (rc = mem.grow(n.lanes, ro.cap_lanes, {BG_BUF(ro.lane, 4), BG_BUF(ro.trows, 32), BG_BUF(ro.tids, 4), BG_BUF(ro.tv, 4)})) ||
+            (rc = mem.grow(n.vtrials, ro.cap_vtrials, {BG_BUF(ro.tluck, 8)})) ||
+            (rc = mem.grow(n.vlanes, ro.cap_vlanes, {BG_BUF(ro.vf, 4 * SRCH_ROLLS)})) ||
+            (rc = mem.grow(n.vpos, ro.cap_vpos, {BG_BUF(ro.f0, 4 * SRCH_ROLLS), BG_BUF(ro.m0, 8)})) ||
+            (rc = mem.grow(n.group, ro.cap_group, {BG_BUF(ro.group, 4)})) ||
+            (rc = mem.grow(n.ctrials, ro.cap_ctrials, {BG_BUF(ro.ctrial, sizeof(cube::Trial)), BG_BUF(ro.ceq, 8)})) ||
+            (rc = mem.grow(n.cstart, ro.cap_cstart, {BG_BUF(ro.cstart, 2 * 4)})))
+            return rc;
+        if (p.cube && !ro.cctr && (rc = mem.alloc(BG_BUF(ro.cctr, cube::CTR_WORDS * 8)))) return rc;
+        if (!ro.host && (rc = mem.alloc_pinned(BG_BUF(ro.host, 8 * 8)))) return rc;        // the pinned words and the two events: first use
+        for (hipEvent_t &e : ro.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return BGAMD_OK;
+    }
+    // the positions as rows; a bad state is refused before anything is played
+    int intake(const int32_t *d_states28, const int32_t *d_turn, const int32_t *d_group)
+    {
+        HIPCHK(hipMemsetAsync(env->a_ctr, 0, A_WORDS * 8, s));
+        HIPCHK(hipMemsetAsync(sc->v.counters, 0, C_COUNT * 8, s));
+        // ... and, in the same pass, a bad group table: the env's copy is written, checked, and read by nothing before the synchronise
+        unsigned long long intake = 0;
+        if (p.grouped) hipLaunchKernelGGL(ro_group_intake_kernel<128>, grid1(p.P, 128), dim3(128), 0, s, d_group, p.P, p.T, ro.group, &env->a_ctr[A_INTAKE]);
+        if (p.cube) cube::intake(s, p.P, env->cube_value, env->cube_owner, ro.cstart, &env->a_ctr[A_INTAKE], (unsigned long long)ERRF_RO_CUBE);
+        const int rc = intake_positions(env, d_states28, d_turn, p.P, ro.pos, s, &intake);
+        if (intake & (ERRF_RO_GROUP | ERRF_RO_CUBE)) return BGAMD_E_INVALID;
+        return rc;
+    }
+    // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1.
+    // Grouped: game id (group_offset + group[p]) T + i, episode group[p] T + i + L - g (ro_refill_kernel); the slot stays jl.
+    int seat(uint64_t seed)
+    {
+        sc->v.seed = seed; sc->v.lane_stride = 1; sc->v.lane_offset = p.lane_offset;
+        r = RoView{p.N, p.T, p.M, p.rotate ? 1 : 0, p.F, ro.pos, ro.fan, ro.fval, ro.lane, ro.tval, ro.tturns, ro.trows, ro.tids, env->a_ctr,
+                   p.grouped ? (const int32_t *)ro.group : nullptr};
+        // plies = 2: the search's virtual roots are scored on THIS env's scratch env, lent to the trial env for the step (search_turn), sized once
+        return p.two_ply ? scratch_env(env, &env->scratch, p.search_scratch_lanes, false, 0, s) : BGAMD_OK;
+    }
+    int search_turn()
+    {
+        sc->scratch = env->scratch;
+        const int e = search_stages(sc, p.run_flags, env->ro_top_k, nullptr, &env->ro_margin, s);
+        env->scratch = sc->scratch;                    // (re-created if it had to grow)
+        sc->scratch = nullptr;
+        return e;
+    }
+    // rotation: the first turn of every (position, ordered pair) as one greedy step with injected dice, L virtual lanes at a time
+    int fan()
+    {
+        for (long long c = 0; c < p.fan_chunks; ++c) {
+            const long long v0 = c * p.L;
+            hipLaunchKernelGGL(ro_fan_seed_kernel, grid1(p.L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, p.n_fan, r);
+            if (const int rc = p.two_ply ? search_turn() : bgamd_env_step_greedy(sc, p.run_flags, 0.0f, BGAMD_F32, s)) return rc;
+            hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(p.L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, p.n_fan, ro.fan);
+            ++steps;
+        }
+        return p.fan_eval ? launch_eval(sc, p.slot, BGAMD_F32, eval_grids(p.n_fan, sc->n_cu), nullptr, p.n_fan, ro.fan, ro.fval, nullptr, nullptr, s)
+                          : BGAMD_OK;
+    }
+    // luck adjustment: the pre-roll evaluation on the search's scratch env -- of the P positions once (rotation: turn 0's luck), then
+    // of the trial lanes before every turn (vr_turn); every trial's luck total starts at 0 or at its turn-0 luck
+    int luck_init()
+    {
+        if (!p.vr) return BGAMD_OK;
+        if (const int rc = preroll_begin(env, p.preroll_lanes, s)) return rc;
+        if (p.rotate) {
+            if (const int rc = preroll_pass(env, p.slot, p.P, ro.pos, nullptr, ro.f0, s)) return rc;
+            hipLaunchKernelGGL(pre_reduce_kernel, grid1(p.P, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)p.P, (const uint4 *)ro.pos, ro.f0,
+                               (float *)nullptr, ro.m0);
+        }
+        hipLaunchKernelGGL(ro_vr_init_kernel, dim3((unsigned)(sc->n_cu * 4)), dim3(RO_NT), 0, s, r, (const float *)ro.f0,
+                           (const double *)ro.m0, ro.tluck);
+        // the cube: every trial's record at its start, with the decision before a rotated turn 0 on the position's own mean
+        if (p.cube) {
+            HIPCHK(hipMemsetAsync(ro.cctr, 0, cube::CTR_WORDS * 8, s));
+            cube::init(s, p.N, p.T, p.rotate ? 1 : 0, ro.pos, ro.cstart, p.P, ro.m0, env->cube_rule, ro.ctrial);
+        }
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    }
+    // (the roots of the turn at hand are in place: the board, side to move and dice of every live trial lane)
+    int vr_turn()
+    {
+        if (const int e = preroll_pass(env, p.slot, p.L, nullptr, &sc->v, ro.vf, s)) return e;
+        hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(p.L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)ro.lane, (const float *)ro.vf, ro.tluck);
+        if (p.cube) cube::turn(s, p.L, sc->v.meta, sc->v.ply, ro.lane, ro.vf, env->cube_rule, ro.ctrial, ro.cctr);
+        return BGAMD_OK;
+    }
+    int refill()
+    {
+        hipLaunchKernelGGL(ro_refill_kernel, grid1(p.L, RO_NT), dim3(RO_NT), 0, s, sc->v, r);
+        if (p.truncates) {                             // truncated trials: the dense fp32 evaluator of bgamd_evaluate_slot
+            const EvalGrids grids = eval_grids(sc->v.n * EST_ROWS, sc->n_cu);        // (the truncated rows are counted on the device: sized as a step's)
+            if (const int e = launch_eval(sc, p.slot, BGAMD_F32, grids, &r.ctr[RO_NTRUNC], p.L, ro.trows, ro.tv, nullptr, nullptr, s)) return e;
+            hipLaunchKernelGGL(ro_trunc_scatter_kernel, dim3((unsigned)sc->n_cu), dim3(RO_NT), 0, s, r, (const float *)ro.tv);
+            HIPCHK(hipMemsetAsync(&r.ctr[RO_NTRUNC], 0, 8, s));
+        }
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    }
+    // (trials done, truncated now, the rollout's error bits, the trial env's error bits) -> dst[0 .. 3], asynchronously
+    int read_back(unsigned long long *dst)
+    {
+        HIPCHK(hipMemcpyAsync(dst, &r.ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(dst + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
+        return BGAMD_OK;
+    }
+    // G runs of R turns with a refill after each, then a read-back into pinned memory; the host waits for the read before the last
+    // one, so the device always has a group queued
+    int turns()
+    {
+        const StepStreams ss{s, sc->tune.overlap ? sc->side : s};
+        RolloutProgress progress(p);
+        for (int k = 0;; ++k) {
+            const int b = k & 1;
+            int e;
+            if ((e = read_back(ro.host + 4 * b))) return e;
+            HIPCHK(hipEventRecord(ro.ev[b], s));
+            if (k > 0) {
+                HIPCHK(hipEventSynchronize(ro.ev[b ^ 1]));
+                const unsigned long long *hp = ro.host + 4 * (b ^ 1);
+                const RolloutProgress::Verdict v = progress.read(hp[0], hp[2], hp[3]);
+                if (v != RolloutProgress::GO_ON) return v == RolloutProgress::FINISHED ? BGAMD_OK : BGAMD_E_INVALID;
+            }
+            for (int gi = 0; gi < p.G; ++gi) {
+                if (p.two_ply) {
+                    // the turn's dice go into the lanes first (the TURN-stream dice of the lane's game id and ply, what BGAMD_ROLL draws):
+                    // the luck pass reads them, and the search step plays them as set dice -- with and without the luck pass
+                    hipLaunchKernelGGL(dice_kernel, grid1(p.L, 256), dim3(256), 0, s, sc->v, (const int32_t *)nullptr, (int32_t *)nullptr, 1);
+                    if ((p.vr && (e = vr_turn())) || (e = search_turn()) || (e = refill())) return e;
+                    steps += 1;
+                    continue;
+                }
+                GreedyRun run;
+                if ((e = run.init(sc, BGAMD_ROLL | p.run_flags, 0.0f, BGAMD_F32)) || (e = run.begin(s))) return e;
+                for (int t = 0; t < p.R; ++t)
+                    if ((p.vr && (e = vr_turn())) || (e = run.step(ss, t + 1 < p.R))) return e;
+                steps += p.R;
+                if ((e = refill())) return e;
+            }
+        }
+    }
+    // every lane empty, the first refill, then the loop; the stream is drained whichever way the loop ended
+    int play()
+    {
+        HIPCHK(hipMemsetAsync(ro.lane, 0xFF, (size_t)p.L * 4, s));
+        if (const int rc = refill()) return rc;
+        const int rc = turns();
+        hipStreamSynchronize(s);
+        return rc;
+    }
+    // the errors of the whole call, the reductions into the caller's outputs, and the record the read calls test
+    int finish(double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated, float *d_trial_value, int32_t *d_trial_turns)
+    {
+        unsigned long long *h = ro.host;
+        int rc;
+        if ((rc = read_back(h))) return rc;
+        HIPCHK(hipMemcpyAsync(h + 4, &sc->v.counters[C_STEPS], 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if ((rc = check_err_flags(sc, h[3]))) return rc;
+        if (h[2] & (ERRF_RO_LONG | ERRF_RO_PLY) || h[0] != (unsigned long long)p.N) return BGAMD_E_INVALID;
+        if (p.vr && (rc = preroll_errors(env, s))) return rc;
+        hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)p.P), dim3(64), 0, s, (long long)p.T, (const float *)ro.tval,
+                           (const uint32_t *)ro.tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
+        // the cube: every trial's cubeful equity into the env's buffer (the paired read's which = 3); the two lane-turn counters
+        unsigned long long h_cube[cube::CTR_WORDS] = {0ull, 0ull};
+        if (p.cube) {
+            cube::reduce(s, p.P, p.T, ro.tval, ro.tturns, ro.ctrial, env->cube_rule, ro.ceq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            HIPCHK(hipMemcpyAsync(h_cube, ro.cctr, sizeof h_cube, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        RolloutResult done{true, p.vr, p.cube, p.grouped, p.P, p.T, env->cube_rule, {p.L, steps, (int64_t)h[4], p.R},
+                           {(int64_t)h_cube[cube::CTR_TURNS], (int64_t)h_cube[cube::CTR_AFTER_DROP]}};
+        if (!p.cube) for (int k = 0; k < 2; ++k) done.cube_info[k] = ro.last.cube_info[k];     // (still those of the last call that had the cube)
+        ro.last = done;
+        return BGAMD_OK;
+    }
+};
+}  // namespace
 
 int bgamd_env_rollout(bgamd_env *env, int flags, const int32_t *d_states28, const int32_t *d_turn, int64_t n_positions,
                       int64_t position_offset, int64_t trials, int64_t max_plies, uint64_t seed, int64_t lanes,
@@ -2287,239 +2486,38 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
                               uint64_t seed, int64_t lanes, double *d_mean, double *d_stderr, int64_t *d_turns, int32_t *d_truncated,
                               float *d_trial_value, int32_t *d_trial_turns, void *stream)
 {
-    if (env) env->ro.vr_P = 0;                         // (bgamd_env_rollout_vr_read: only after a call that had the flag)
-    if (env) env->ro.out_P = 0;                        // (bgamd_env_rollout_outcomes_read: only after a call that succeeded)
-    if (env) env->ro.cube_P = 0;                       // (bgamd_env_rollout_cube_read: only after a call that had the cube on)
-    if (!env || !d_states28 || n_positions < 1 || trials < 1 || max_plies < 0 || lanes < 0 || position_offset < 0) return BGAMD_E_INVALID;
-    if (flags & ~(BGAMD_ROLLOUT_ROTATE | BGAMD_WEIGHTS_SLOT1 | BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
-    if (n_positions >= (1ll << 31) || trials >= (1ll << 31) || n_positions * trials >= (1ll << 31) || lanes > (1ll << 30))
-        return BGAMD_E_INVALID;
-    // the cube rides on the luck pass's pre-roll means: without them there is nothing to decide on
-    const bool cube_on = (env->cube_flags & BGAMD_CUBE_ON) != 0;
-    if (cube_on && !(flags & BGAMD_ROLLOUT_VR)) return BGAMD_E_INVALID;
+    if (!env) return BGAMD_E_INVALID;
+    env->ro.last.ok = false;                           // the read calls refuse until a call has succeeded again
+    const RolloutPlan plan = rollout_plan(RolloutRequest{flags, n_positions, position_offset, trials, max_plies, lanes, d_states28 != nullptr,
+                                                         d_group != nullptr, env->ro_plies, env->ro_top_k, (env->cube_flags & BGAMD_CUBE_ON) != 0,
+                                                         {env->net.has_weights[0], env->net.has_weights[1]}}, RO_TURN_LIMIT);
+    if (plan.rc) return plan.rc;
     HIPCHK(hipSetDevice(env->device));
-    const int slot = (flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0;
-    if (!env->net.has_weights[slot]) return BGAMD_E_NOWEIGHTS;
-    hipStream_t s = (hipStream_t)stream;
-    const long long P = n_positions, T = trials, N = P * T, M = max_plies;
-    const bool rotate = (flags & BGAMD_ROLLOUT_ROTATE) != 0, vr = (flags & BGAMD_ROLLOUT_VR) != 0;
-    const long long F = rotate ? (T < 36 ? T : 36) : 0, n_fan = P * F;
-    const long long L = lanes > 0 ? lanes : (N < ROLLOUT_LANES ? ((N + 255) / 256) * 256 : ROLLOUT_LANES);
-    RolloutState &ro = env->ro;
+    RolloutCall call{env, plan, (hipStream_t)stream, env->ro};
     int rc;
-
-    // the scratch env (exactly L lanes) and the buffers of this call
-    if ((rc = scratch_env(env, &env->rscratch, L, true, 1, s))) return rc;
-    bgamd_env *sc = env->rscratch;
-    DevMem &mem = env->mem;
-    if ((rc = mem.grow(P, ro.cap_pos, {BG_BUF(ro.pos, 32)})) ||
-        (rc = mem.grow(n_fan, ro.cap_fan, {BG_BUF(ro.fan, 32), BG_BUF(ro.fval, 4)})) ||
-        (rc = mem.grow(N, ro.cap_trials, {BG_BUF(ro.tval, 4), BG_BUF(ro.tturns, 4)})) ||
-        (rc = mem.grow(L, ro.cap_lanes, {BG_BUF(ro.lane, 4), BG_BUF(ro.trows, 32), BG_BUF(ro.tids, 4), BG_BUF(ro.tv, 4)})))
+    if ((rc = call.buffers()) || (rc = call.intake(d_states28, d_turn, d_group)) || (rc = call.seat(seed)) ||
+        (rc = call.fan()) || (rc = call.luck_init()) || (rc = call.play()))        // turn 0 (the rotation fan, the luck and cube records), then the trials
         return rc;
-    if (vr && ((rc = mem.grow(N, ro.cap_vtrials, {BG_BUF(ro.tluck, 8)})) ||
-               (rc = mem.grow(L, ro.cap_vlanes, {BG_BUF(ro.vf, 4 * SRCH_ROLLS)})) ||
-               (rc = mem.grow(P, ro.cap_vpos, {BG_BUF(ro.f0, 4 * SRCH_ROLLS), BG_BUF(ro.m0, 8)}))))
-        return rc;
-    if (d_group && (rc = mem.grow(P, ro.cap_group, {BG_BUF(ro.group, 4)}))) return rc;
-    if (cube_on && ((rc = mem.grow(N, ro.cap_ctrials, {BG_BUF(ro.ctrial, sizeof(cube::Trial)), BG_BUF(ro.ceq, 8)})) ||
-                    (rc = mem.grow(P, ro.cap_cstart, {BG_BUF(ro.cstart, 2 * 4)})) ||
-                    (!ro.cctr && (rc = mem.alloc(BG_BUF(ro.cctr, cube::CTR_WORDS * 8))))))
-        return rc;
-    const cube::Rule cube_rule = env->cube_rule;
-    if (!ro.host && (rc = mem.alloc_pinned(BG_BUF(ro.host, 8 * 8)))) return rc;        // the pinned words and the two events: first use
-    for (hipEvent_t &e : ro.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    unsigned long long *h = ro.host, *ctr = env->a_ctr;
-
-    // the positions as rows; a bad state is refused before anything is played
-    HIPCHK(hipMemsetAsync(env->a_ctr, 0, A_WORDS * 8, s));
-    HIPCHK(hipMemsetAsync(sc->v.counters, 0, C_COUNT * 8, s));
-    // ... and, in the same pass, a bad group table: the env's copy is written, checked, and read by nothing before the synchronise
-    unsigned long long intake = 0;
-    if (d_group) hipLaunchKernelGGL(ro_group_intake_kernel<128>, grid1(P, 128), dim3(128), 0, s, d_group, P, T, ro.group, &env->a_ctr[A_INTAKE]);
-    if (cube_on) cube::intake(s, P, env->cube_value, env->cube_owner, ro.cstart, &env->a_ctr[A_INTAKE], (unsigned long long)ERRF_RO_CUBE);
-    rc = intake_positions(env, d_states28, d_turn, P, ro.pos, s, &intake);
-    if (intake & (ERRF_RO_GROUP | ERRF_RO_CUBE)) return BGAMD_E_INVALID;
-    if (rc) return rc;
-
-    // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1.
-    // Grouped: game id (group_offset + group[p]) T + i, episode group[p] T + i + L - g (ro_refill_kernel); the slot stays jl.
-    sc->v.seed = seed;
-    sc->v.lane_stride = 1;
-    sc->v.lane_offset = (unsigned long long)position_offset * (unsigned long long)T - (unsigned long long)L;
-    const RoView r{N, T, M, rotate ? 1 : 0, F, ro.pos, ro.fan, ro.fval, ro.lane, ro.tval, ro.tturns, ro.trows, ro.tids, ctr,
-                   d_group ? (const int32_t *)ro.group : nullptr};
-    const int run_flags = flags & BGAMD_WEIGHTS_SLOT1;
-    const StepStreams ss{s, sc->tune.overlap ? sc->side : s};
-    long long steps = 0;
-
-    // plies = 2 (bgamd_env_rollout_policy): every turn is one filtered search step of the trial env.  Its virtual roots are scored on
-    // THIS env's scratch env, lent to the trial env for the step: the luck pass uses the same one between the steps (everything is
-    // stream-ordered), and a second env of up to SEARCH_CHUNK lanes (~3.4 GB) would buy nothing.  It is sized once, for top_k (8 when
-    // there is no limit) candidates per lane, so that a turn with many candidates does not re-create it; the search's per-lane and
-    // candidate buffers of the trial env come to ~0.2 GB at 65 536 lanes and top_k 5 (2 x 67 MB of row indices and ranks, 43 MB of candidates).
-    const bool two_ply = env->ro_plies == 2;
-    const int pol_k = env->ro_top_k;
-    const float pol_margin = env->ro_margin;
-    if (two_ply && (rc = scratch_env(env, &env->scratch, search_lanes(L * (long long)(pol_k > 0 ? pol_k : 8) * SRCH_ROLLS), false, 0, s))) return rc;
-    auto search_turn = [&](int fl) -> int {
-        sc->scratch = env->scratch;
-        const int e = search_stages(sc, fl, pol_k, nullptr, &pol_margin, s);
-        env->scratch = sc->scratch;                    // (re-created if it had to grow)
-        sc->scratch = nullptr;
-        return e;
-    };
-
-    // rotation: the first turn of every (position, ordered pair) as one greedy step with injected dice, L virtual lanes at a time
-    if (rotate) {
-        for (long long v0 = 0; v0 < n_fan; v0 += L) {
-            hipLaunchKernelGGL(ro_fan_seed_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, r);
-            if ((rc = two_ply ? search_turn(run_flags) : bgamd_env_step_greedy(sc, run_flags, 0.0f, BGAMD_F32, s))) return rc;
-            hipLaunchKernelGGL(ro_fan_collect_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, v0, n_fan, ro.fan);
-            ++steps;
-        }
-        if (M == 1 && (rc = launch_eval(sc, slot, BGAMD_F32, eval_grids(n_fan, sc->n_cu), nullptr, n_fan, ro.fan, ro.fval, nullptr, nullptr, s))) return rc;
-    }
-
-    // luck adjustment: the pre-roll evaluation on the search's scratch env -- of the P positions once (rotation: turn 0's luck), then
-    // of the trial lanes before every turn (vr_turn); every trial's luck total starts at 0 or at its turn-0 luck
-    if (vr) {
-        if ((rc = preroll_begin(env, (rotate ? P : 0) > L ? P : L, s))) return rc;
-        if (rotate) {
-            if ((rc = preroll_pass(env, slot, P, ro.pos, nullptr, ro.f0, s))) return rc;
-            hipLaunchKernelGGL(pre_reduce_kernel, grid1(P, SRCH_NT), dim3(SRCH_NT), 0, s, (long long)P, (const uint4 *)ro.pos, ro.f0,
-                               (float *)nullptr, ro.m0);
-        }
-        hipLaunchKernelGGL(ro_vr_init_kernel, dim3((unsigned)(sc->n_cu * 4)), dim3(RO_NT), 0, s, r, (const float *)ro.f0,
-                           (const double *)ro.m0, ro.tluck);
-        // the cube: every trial's record at its start, with the decision before a rotated turn 0 on the position's own mean
-        if (cube_on) {
-            HIPCHK(hipMemsetAsync(ro.cctr, 0, cube::CTR_WORDS * 8, s));
-            cube::init(s, N, T, rotate ? 1 : 0, ro.pos, ro.cstart, P, ro.m0, cube_rule, ro.ctrial);
-        }
-        HIPCHK(hipGetLastError());
-    }
-    // (the roots of the turn at hand are in place: the board, side to move and dice of every live trial lane)
-    auto vr_turn = [&]() -> int {
-        if (const int e = preroll_pass(env, slot, L, nullptr, &sc->v, ro.vf, s)) return e;
-        hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)ro.lane, (const float *)ro.vf, ro.tluck);
-        if (cube_on) cube::turn(s, L, sc->v.meta, sc->v.ply, ro.lane, ro.vf, cube_rule, ro.ctrial, ro.cctr);
-        return BGAMD_OK;
-    };
-
-    // refill points every R turns; M > 0: R divides M - (first ply), so every trial's M-th turn ends a run
-    int R = ROLLOUT_RUN;
-    if (M > 0) {
-        const long long D = M - (rotate ? 1 : 0);
-        R = D < 1 ? 1 : (int)(D < ROLLOUT_RUN ? D : ROLLOUT_RUN);
-        while (D > 0 && D % R) --R;
-    }
-    if (two_ply) R = 1;                                // a search turn is a step of its own: a refill after every turn
-    const int G = R >= 16 ? 1 : 16 / R;                // runs between two reads of the trials-done counter (~16 turns)
-    const EvalGrids trunc_grids = eval_grids(sc->v.n * EST_ROWS, sc->n_cu);      // (the truncated rows are counted on the device: sized as a step's)
-    auto refill = [&]() -> int {
-        hipLaunchKernelGGL(ro_refill_kernel, grid1(L, RO_NT), dim3(RO_NT), 0, s, sc->v, r);
-        if (M > 0) {                                   // truncated trials: the dense fp32 evaluator of bgamd_evaluate_slot
-            if (const int e = launch_eval(sc, slot, BGAMD_F32, trunc_grids, &ctr[RO_NTRUNC], L, ro.trows, ro.tv, nullptr, nullptr, s)) return e;
-            hipLaunchKernelGGL(ro_trunc_scatter_kernel, dim3((unsigned)sc->n_cu), dim3(RO_NT), 0, s, r, (const float *)ro.tv);
-            HIPCHK(hipMemsetAsync(&ctr[RO_NTRUNC], 0, 8, s));
-        }
-        HIPCHK(hipGetLastError());
-        return BGAMD_OK;
-    };
-    HIPCHK(hipMemsetAsync(ro.lane, 0xFF, (size_t)L * 4, s));
-    if ((rc = refill())) return rc;
-
-    // (trials done, truncated now, the rollout's error bits, the trial env's error bits) -> dst[0 .. 3], asynchronously
-    auto read_back = [&](unsigned long long *dst) -> int {
-        HIPCHK(hipMemcpyAsync(dst, &ctr[RO_DONE], 3 * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(dst + 3, &sc->v.counters[C_ERR], 8, hipMemcpyDeviceToHost, s));
-        return BGAMD_OK;
-    };
-    // the loop: G runs of R turns with a refill after each, then a read-back into pinned memory; the host waits for the read before
-    // the last one, so the device always has a group queued
-    auto loop = [&]() -> int {
-        unsigned long long last_done = 0;
-        long long stalled = 0;
-        for (int k = 0;; ++k) {
-            const int b = k & 1;
-            int e;
-            if ((e = read_back(h + 4 * b))) return e;
-            HIPCHK(hipEventRecord(ro.ev[b], s));
-            if (k > 0) {
-                HIPCHK(hipEventSynchronize(ro.ev[b ^ 1]));
-                const unsigned long long *hp = h + 4 * (b ^ 1);
-                if (hp[0] >= (unsigned long long)N || hp[2] || hp[3]) return BGAMD_OK;
-                stalled = hp[0] == last_done ? stalled + (long long)G * R : 0;
-                last_done = hp[0];
-                if (stalled > (long long)RO_TURN_LIMIT + 64) return BGAMD_E_INVALID;      // (cannot happen: the kernels' own limit fires first)
-            }
-            for (int gi = 0; gi < G; ++gi) {
-                if (two_ply) {
-                    // the turn's dice go into the lanes first (the TURN-stream dice of the lane's game id and ply, what BGAMD_ROLL draws):
-                    // the luck pass reads them, and the search step plays them as set dice -- with and without the luck pass
-                    hipLaunchKernelGGL(dice_kernel, grid1(L, 256), dim3(256), 0, s, sc->v, (const int32_t *)nullptr, (int32_t *)nullptr, 1);
-                    if ((vr && (e = vr_turn())) || (e = search_turn(run_flags)) || (e = refill())) return e;
-                    steps += 1;
-                    continue;
-                }
-                GreedyRun run;
-                if ((e = run.init(sc, BGAMD_ROLL | run_flags, 0.0f, BGAMD_F32)) || (e = run.begin(s))) return e;
-                for (int t = 0; t < R; ++t)
-                    if ((vr && (e = vr_turn())) || (e = run.step(ss, t + 1 < R))) return e;
-                steps += R;
-                if ((e = refill())) return e;
-            }
-        }
-    };
-    rc = loop();
-    hipStreamSynchronize(s);
-    if (rc) return rc;
-
-    if ((rc = read_back(h))) return rc;
-    HIPCHK(hipMemcpyAsync(h + 4, &sc->v.counters[C_STEPS], 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if ((rc = check_err_flags(sc, h[3]))) return rc;
-    if (h[2] & (ERRF_RO_LONG | ERRF_RO_PLY) || h[0] != (unsigned long long)N) return BGAMD_E_INVALID;
-    if (vr && (rc = preroll_errors(env, s))) return rc;
-    ro.info[0] = L; ro.info[1] = steps; ro.info[2] = (int64_t)h[4]; ro.info[3] = R;
-
-    hipLaunchKernelGGL(ro_reduce_kernel, dim3((unsigned)P), dim3(64), 0, s, (long long)T, (const float *)ro.tval,
-                       (const uint32_t *)ro.tturns, d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
-    // the cube: every trial's cubeful equity into the env's buffer (the paired read's which = 3); the two lane-turn counters
-    unsigned long long h_cube[cube::CTR_WORDS] = {0ull, 0ull};
-    if (cube_on) {
-        cube::reduce(s, P, T, ro.tval, ro.tturns, ro.ctrial, cube_rule, ro.ceq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-        HIPCHK(hipMemcpyAsync(h_cube, ro.cctr, sizeof h_cube, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    if (cube_on) {
-        ro.cube_P = P; ro.cube_T = T; ro.cube_rule = cube_rule;
-        ro.cube_info[0] = (int64_t)h_cube[cube::CTR_TURNS]; ro.cube_info[1] = (int64_t)h_cube[cube::CTR_AFTER_DROP];
-    }
-    if (vr) { ro.vr_P = P; ro.vr_T = T; }
-    ro.out_P = P; ro.out_T = T;
-    ro.grouped = d_group != nullptr;
-    return BGAMD_OK;
+    return call.finish(d_mean, d_stderr, d_turns, d_truncated, d_trial_value, d_trial_turns);
 }
 
 int bgamd_env_rollout_paired_read(bgamd_env *env, const int32_t *d_ref, int which, double *d_diff_mean, double *d_diff_stderr, void *stream)
 {
     ENV_GUARD(env);
-    if (env->ro.out_P < 1 || !d_ref || which < 0 || which > 3) return BGAMD_E_INVALID;
-    if (which == 1 && env->ro.vr_P < 1) return BGAMD_E_INVALID;
     const RolloutState &ro = env->ro;
+    const RolloutResult &last = ro.last;
+    if (!last.ok || !d_ref || which < 0 || which > 3) return BGAMD_E_INVALID;
+    if (which == 1 && !last.vr) return BGAMD_E_INVALID;
+    const int32_t *group = last.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr;
     if (which == 3) {                                  // the cubeful equity: the buffer the cubeful rollout's reduce launch left (bg_cube.h)
-        if (ro.cube_P < 1) return BGAMD_E_INVALID;
-        cube::paired((hipStream_t)stream, ro.cube_P, ro.cube_T, d_ref, ro.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr,
-                     ro.ceq, d_diff_mean, d_diff_stderr);
+        if (!last.cube) return BGAMD_E_INVALID;
+        cube::paired((hipStream_t)stream, last.P, last.T, d_ref, group, ro.ceq, d_diff_mean, d_diff_stderr);
         HIPCHK(hipGetLastError());
         return BGAMD_OK;
     }
-    hipLaunchKernelGGL(ro_pair_reduce_kernel<64>, dim3((unsigned)ro.out_P), dim3(64), 0, (hipStream_t)stream, (long long)ro.out_P,
-                       (long long)ro.out_T, which, d_ref, ro.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr,
-                       (const float *)ro.tval, (const uint32_t *)ro.tturns, (const double *)ro.tluck, d_diff_mean, d_diff_stderr);
+    hipLaunchKernelGGL(ro_pair_reduce_kernel<64>, dim3((unsigned)last.P), dim3(64), 0, (hipStream_t)stream, (long long)last.P,
+                       (long long)last.T, which, d_ref, group, (const float *)ro.tval, (const uint32_t *)ro.tturns, (const double *)ro.tluck,
+                       d_diff_mean, d_diff_stderr);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
 }
@@ -2556,8 +2554,8 @@ int bgamd_env_rollout_cube_read(bgamd_env *env, double *d_cubeful, double *d_cub
 {
     ENV_GUARD(env);
     const RolloutState &ro = env->ro;
-    if (ro.cube_P < 1) return BGAMD_E_INVALID;
-    cube::reduce((hipStream_t)stream, ro.cube_P, ro.cube_T, ro.tval, ro.tturns, ro.ctrial, ro.cube_rule, ro.ceq, d_cubeful, d_cubeful_stderr,
+    if (!ro.last.ok || !ro.last.cube) return BGAMD_E_INVALID;
+    cube::reduce((hipStream_t)stream, ro.last.P, ro.last.T, ro.tval, ro.tturns, ro.ctrial, ro.last.cube_rule, ro.ceq, d_cubeful, d_cubeful_stderr,
                  d_counts, d_trial_cubeful, d_trial_cube, d_trial_dropped);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
@@ -2566,22 +2564,22 @@ int bgamd_env_rollout_cube_read(bgamd_env *env, double *d_cubeful, double *d_cub
 int bgamd_env_rollout_cube_info(bgamd_env *env, int64_t h_out[2])
 {
     if (!env || !h_out) return BGAMD_E_INVALID;
-    h_out[0] = env->ro.cube_info[0]; h_out[1] = env->ro.cube_info[1];
+    h_out[0] = env->ro.last.cube_info[0]; h_out[1] = env->ro.last.cube_info[1];
     return BGAMD_OK;
 }
 
 int bgamd_env_rollout_info(bgamd_env *env, int64_t h_out[4])
 {
     if (!env || !h_out) return BGAMD_E_INVALID;
-    for (int k = 0; k < 4; ++k) h_out[k] = env->ro.info[k];
+    for (int k = 0; k < 4; ++k) h_out[k] = env->ro.last.info[k];
     return BGAMD_OK;
 }
 
 int bgamd_env_rollout_vr_read(bgamd_env *env, double *d_vr_mean, double *d_vr_stderr, double *d_trial_luck, void *stream)
 {
     ENV_GUARD(env);
-    if (env->ro.vr_P < 1) return BGAMD_E_INVALID;
-    hipLaunchKernelGGL(ro_vr_reduce_kernel, dim3((unsigned)env->ro.vr_P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.vr_T,
+    if (!env->ro.last.ok || !env->ro.last.vr) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL(ro_vr_reduce_kernel, dim3((unsigned)env->ro.last.P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.last.T,
                        (const float *)env->ro.tval, (const double *)env->ro.tluck, d_vr_mean, d_vr_stderr, d_trial_luck);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;
@@ -2591,8 +2589,8 @@ int bgamd_env_rollout_outcomes_read(bgamd_env *env, int64_t *d_counts, double *d
                                     int8_t *d_trial_points, void *stream)
 {
     ENV_GUARD(env);
-    if (env->ro.out_P < 1) return BGAMD_E_INVALID;
-    hipLaunchKernelGGL((ro_outcome_reduce_kernel<0>), dim3((unsigned)env->ro.out_P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.out_T,
+    if (!env->ro.last.ok) return BGAMD_E_INVALID;
+    hipLaunchKernelGGL((ro_outcome_reduce_kernel<0>), dim3((unsigned)env->ro.last.P), dim3(64), 0, (hipStream_t)stream, (long long)env->ro.last.T,
                        (const float *)env->ro.tval, (const uint32_t *)env->ro.tturns, d_counts, d_equity, d_equity_stderr, d_trial_points);
     HIPCHK(hipGetLastError());
     return BGAMD_OK;

@@ -1,5 +1,5 @@
-"""The host schedule of bgamd_env_rollout restated in plain Python (from include/bgamd.h and the comments of bgamd_env_rollout in
-csrc/bgamd.hip), and the cases the edge tests run: the horizon table, the position sets and the fp64 reference of the calls that are
+"""The host schedule of bgamd_env_rollout restated in plain Python (from include/bgamd.h and the rules of rollout_plan in
+csrc/bg_rollout_plan.h), and the cases the edge tests run: the horizon table, the position sets and the fp64 reference of the calls that are
 compared with it.  No device, no torch.  Shared by tests/test_rollout_cases_cpu.py, which states the conditions the GPU tests rest on,
 and tests/test_gpu_rollout_edges.py."""
 import functools

@@ -6,7 +6,8 @@
   (d) a fan of exactly one chunk, one entry more, one less than two, several chunks; more positions than lanes with the luck pass;
   (e) the seat loop: trials that are over before a lane plays them outnumber the lanes many times over;
   (f) nothing of one call's buffers shows in the next;
-  (g) the luck and the 2-ply policy at the shortest horizons and at run length 1.
+  (g) the luck and the 2-ply policy at the shortest horizons and at run length 1;
+  (h) every read call answers for the last rollout call alone: plain, with luck and cube, refused, ungrouped after grouped.
 The conditions these tests rest on (what the horizons cover, what the positions are, how few near ties the reference meets) are checked
 on the CPU: tests/test_rollout_cases_cpu.py.  Everything is bit equality, except a truncated trial's fp32 value against fp64 (1e-5)."""
 import numpy as np
@@ -348,3 +349,66 @@ def test_two_plies_at_the_edges(bg, W, env, positions, monkeypatch, M, rotate, T
     np.testing.assert_array_equal(r["trial_points"], points)
     np.testing.assert_array_equal(r["truncated"], trunc)
     assert trunc[0] == T and (turns[3] == 0).all()
+
+
+# ---- (h) the read calls follow the last call ---------------------------------------------------------------------------------------------------
+
+def test_reads_follow_the_last_call(bg, W, positions):
+    """One env, four calls in sequence: what each read call returns or refuses is decided by the LAST rollout call alone -- a plain one,
+    a luck-adjusted one with the cube, one refused for a bad state (every read refuses; the two info calls keep the numbers of the last
+    call that succeeded), and an ungrouped call after a grouped one (no trace of the group table)."""
+    from backgammon_env import _capi
+    st, tu, _ = positions
+    st, tu = st[:3], tu[:3]
+    T, ref = 40, [1, 1, 0]
+    args = dict(max_plies=3, lanes=256, seed=SEED)
+
+    def vr_read(e):
+        _capi.check(e._lib.bgamd_env_rollout_vr_read(e._h, None, None, None, None), "rollout_vr_read")
+
+    def refuses(call):
+        with pytest.raises(bg.BgamdError, match="-1"):
+            call()
+
+    e = bg.VecGame(64, seed=7)
+    e.load_weights(W)
+    # 1. a plain call
+    e.rollout(st, tu, T, **args)
+    assert e.rollout_outcomes_read()["counts"].shape == (3, 6)
+    e.rollout_paired(ref, "value")
+    e.rollout_paired(ref, "equity")
+    for call in (lambda: vr_read(e), e.rollout_cube_read, lambda: e.rollout_paired(ref, "cubeful"), lambda: e.rollout_paired(ref, "vr")):
+        refuses(call)
+    # 2. luck-adjusted, the cube on: every read works
+    e.rollout(st, tu, T, variance_reduction=True, cube=bg.Cube(), **args)
+    vr_read(e)
+    assert e.rollout_cube_read()["cubeful"].shape == (3,) and e.rollout_outcomes_read(per_trial=True)["trial_points"].shape == (3, T)
+    for which in ("value", "vr", "equity", "cubeful"):
+        e.rollout_paired(ref, which)
+    info, cube_info = e.rollout_info(), e.rollout_cube_info()
+    assert info[0] == 256 and info[3] == RC.run_length(3, True) and info[1] > 0 and info[2] > 0 and cube_info[0] > 0
+    # 3. a call refused for a bad state (one checker too many): nothing to read, the infos as they were
+    bad = st.copy()
+    bad[1, 3] = 16
+    with pytest.raises(bg.BgamdError, match="-5"):
+        e.rollout(bad, tu, T, variance_reduction=True, cube=bg.Cube(), **args)
+    for call in (lambda: vr_read(e), e.rollout_cube_read, e.rollout_outcomes_read, *(lambda w=w: e.rollout_paired(ref, w) for w in e.PAIRED_WHICH)):
+        refuses(call)
+    assert e.rollout_info() == info and e.rollout_cube_info() == cube_info
+    # 4. grouped, then ungrouped with the same positions: the paired read pairs what a fresh env pairs
+    e.rollout(st, tu, T, variance_reduction=True, groups=[0, 0, 1], **args)
+    grouped = _np(dict(zip("ms", e.rollout_paired(ref, "vr"))))
+    assert np.isfinite(grouped["m"][:2]).all() and np.isnan(grouped["m"][2])                # positions 0 and 1 share dice, 2 and 0 do not
+    e.rollout(st, tu, T, variance_reduction=True, **args)
+    after = {w: _np(dict(zip("ms", e.rollout_paired(ref, w)))) for w in ("value", "vr", "equity")}
+    assert e.stats()["error_flags"] == 0
+    e.close()
+    f = bg.VecGame(64, seed=7)
+    f.load_weights(W)
+    f.rollout(st, tu, T, variance_reduction=True, **args)
+    for w in after:
+        fresh = _np(dict(zip("ms", f.rollout_paired(ref, w))))
+        for k in "ms":
+            np.testing.assert_array_equal(after[w][k].view(np.int64), fresh[k].view(np.int64), err_msg=w + k)
+        assert np.isnan(after[w]["m"][[0, 2]]).all() and after[w]["m"][1] == 0              # ungrouped: a position pairs with itself only
+    f.close()
