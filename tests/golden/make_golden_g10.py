@@ -5,7 +5,7 @@
   g10_arbitrary_boards.npz   positions that play never reaches -- tests/helpers.random_boards(1500, 7, with_bar=False): random
         placement, heavy stacks, late bear-off boards -- with (player, die1, die2) drawn from RandomState(8), every fifth a double.
         For each: the reference's evaluateTurnSequences (ordered sequences, afterstates) and legalMoves for the dice 1, 4 and 6.
-        The binding cannot set bar counts, so those stay 0 (bar positions are pinned by G1/G3).
+        The bar counts stay 0 here; make_golden_g11.py builds bar counts 0..15 through hits and records the bar-heavy boards.
 
     python tests/golden/make_golden_g10.py
 """

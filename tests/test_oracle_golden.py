@@ -245,8 +245,9 @@ def test_g5_greedy_trajectories(golden_dir, weights):
 def test_oracle_vs_compiled_reference_on_arbitrary_boards(golden_dir):
     """Positions that play never reaches (random placement, heavy stacks, late bear-off boards): the oracle
     against the UNMODIFIED reference -- its answers on these boards are fixture G10 (tests/golden/make_golden_g10.py,
-    from the reference compiled into oracle/_ref), and wherever that module is present it is asked as well (the
-    binding cannot set bar counts, so those stay 0 here; bar positions are pinned by G1/G3)."""
+    from the reference compiled into oracle/_ref), and wherever that module is present it is asked as well.  The bar counts
+    stay 0 here.  (The binding has no setter for them, but hits through setGameBoard + tryMove reach every pair of bar counts:
+    tests/rule_cases.py, fixture G11 and tests/test_rule_cases_cpu.py hold the oracle to the reference on bars 0..15.)"""
     import importlib.util
     import sys
     from helpers import random_boards
