@@ -6,6 +6,8 @@ def random_boards(n, seed, with_bar=True):
     """Arbitrary (not necessarily reachable) positions: random checker placement, bars and borne-off counts,
     heavy stacks, late bear-off boards, both sides on the bar.  A bar holds 0, 1 or 2 checkers here, never more (rng.randint(0, 3)):
     bar counts 3..15, entries that use three or four dice and hits that carry a bar count across 3|4 and 7|8 are in tests/rule_cases.py.
+    Kind 1 keeps PLAYER1 on 19..24 and PLAYER2 on 1..6, so a mover that bears off with an opposing checker inside its home board -- where
+    the overrun rule differs between the sides -- hardly occurs here: the end-game set is tests/endgame_cases.py.
     The stream of this generator is left as it is: fixture G10 and the tests that share its boards depend on it."""
     rng = np.random.RandomState(seed)
     st = np.zeros((n, 28), dtype=np.int32)

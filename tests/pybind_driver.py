@@ -5,6 +5,7 @@ test process that name may already be taken by the Python package or by the refe
 
     python tests/pybind_driver.py surface         -> checks the exported surface (no GPU needed), prints OK
     python tests/pybind_driver.py games <n>       -> plays fixture G3's first n games through it, prints 'OK turns seconds'
+    python tests/pybind_driver.py endgame         -> 64 end-game lanes of fixture G12 through it, prints 'OK sequences-played games-ended'
 """
 import os
 import sys
@@ -102,5 +103,14 @@ def games(n):
     print("OK", turns, "%.3f" % dt)
 
 
+def endgame():
+    """The end-game lanes of tests/endgame_cases.scalar_lanes through the compiled module, against fixture G12"""
+    import numpy as np
+    import endgame_cases as EC                                # (beside this file)
+    g12 = dict(np.load(os.path.join(ROOT, "tests", "golden", "g12_endgame_boards.npz")))
+    played, ended = EC.scalar_surface_check(bg, g12, EC.scalar_lanes(g12["boards"]))
+    print("OK", played, ended)
+
+
 if __name__ == "__main__":
-    surface() if sys.argv[1] == "surface" else games(int(sys.argv[2]))
+    {"surface": surface, "endgame": endgame}[sys.argv[1]]() if sys.argv[1] != "games" else games(int(sys.argv[2]))

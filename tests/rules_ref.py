@@ -16,25 +16,40 @@ Variants (`wrong=`):
   "e"  bar counts kept modulo 4
   "f"  an entering checker does not hit: the blot leaves the point but never reaches the bar
   "g"  the second-die-first block is dropped when both dice enter from the bar
+and of the end-game rules (ENDGAME_VARIANTS; tests/test_endgame_cases_cpu.py holds them to the set of tests/endgame_cases.py):
+  "h"  PLAYER2's overrun judged by PLAYER1's rule: only its own checkers on origin+1..7 deny it
+  "i"  PLAYER1's overrun judged by PLAYER2's rule: a checker of either colour on origin+1..24 denies it
+  "j"  PLAYER2's block range ends at point 6, not 7
+  "k"  an overrun is always legal          "l"  an overrun is never legal
+  "m"  bear-off allowed with a checker outside the home board
+  "n"  bear-off allowed from a point while the mover is on the bar
+  "o"  play goes on after the fifteenth checker is off: the turn passes and the game is not over (turn_end)
+  "p"  no hit inside the mover's home board: an opposing blot there blocks like a made point
 """
 
 VARIANTS = ("a", "b", "c", "d", "e", "f", "g")
+ENDGAME_VARIANTS = ("h", "i", "j", "k", "l", "m", "n", "o", "p")
+MESSAGES = ("", "Invalid origin", "Origin out of range", "Destination out of range", "Cannot move in that direction.",
+            "Move does not match dice.", "Invalid destination.", "Cannot bear off from jail")
 
 
-def _can_bear_off(s, player, die, origin):
+def _can_bear_off(s, player, die, origin, wrong=None):
     """a5 with Q1: bar empty, every checker home, and an overrun only when nothing sits behind -- PLAYER1's overrun is blocked by its own
     checkers on the higher points, PLAYER2's by ANY checker on the points origin+1..7."""
-    if s[24 + player] != 0:
+    if s[24 + player] != 0 and wrong != "n":
         return False
-    if player == 0:
-        if any(s[p - 1] > 0 for p in range(1, 19)):
-            return False
-        if die > 25 - origin and any(s[p - 1] > 0 for p in range(origin + 1, 25)):
-            return False
-    else:
-        if any(s[p - 1] < 0 for p in range(7, 25)):
-            return False
-        if die > origin and any(s[p - 1] != 0 for p in range(origin + 1, 8)):
+    outside = range(1, 19) if player == 0 else range(7, 25)
+    sign = 1 if player == 0 else -1
+    if wrong != "m" and any(s[p - 1] * sign > 0 for p in outside):
+        return False
+    if die > (25 - origin if player == 0 else origin):
+        if wrong in ("k", "l"):
+            return wrong == "k"
+        above = range(origin + 1, 25) if player == 0 else range(origin + 1, 7 if wrong == "j" else 8)
+        either = player == 1                                  # PLAYER2's rule looks at both colours, PLAYER1's at its own
+        if (wrong == "h" and player == 1) or (wrong == "i" and player == 0):
+            either = not either
+        if any((s[p - 1] != 0) if either else (s[p - 1] * sign > 0) for p in above):
             return False
     return True
 
@@ -45,8 +60,11 @@ def legal_moves(s, player, die, entered=False, wrong=None):
     bar_origin = 0 if player == 0 else 25
     on_bar = s[24 + player] > 0
     out = []
+    home = range(19, 25) if player == 0 else range(1, 7)
     for o in range(26):
         if on_bar and o != bar_origin and not (wrong == "a" and entered):
+            if wrong == "n" and 1 <= o <= 24 and s[o - 1] * sign > 0 and not 1 <= o + sign * die <= 24 and _can_bear_off(s, player, die, o, wrong):
+                out.append((o, min(25, max(0, o + sign * die))))
             continue
         if o == bar_origin:
             if not on_bar:
@@ -55,9 +73,9 @@ def legal_moves(s, player, die, entered=False, wrong=None):
             continue
         d = min(25, max(0, o + sign * die))
         if d == 0 or d == 25:
-            ok = _can_bear_off(s, player, die, o)
+            ok = _can_bear_off(s, player, die, o, wrong)
         else:
-            ok = s[d - 1] * sign >= -1
+            ok = s[d - 1] * sign >= (0 if wrong == "p" and d in home else -1)
         if ok:
             out.append((o, d))
     return out
@@ -126,3 +144,40 @@ def turn_sequences(s, player, d1, d2, wrong=None):
     if wrong == "c" and seqs == [[]]:
         return [], []
     return seqs, states
+
+
+def turn_end(after, player, wrong=None):
+    """a4 after a turn of `player` that left `after`: -> (over, winner or -1, the side to move next: the winner's turn stays)"""
+    if wrong != "o":
+        for pl in (0, 1):
+            if after[26 + pl] == 15:
+                return True, pl, player
+    return False, -1, 1 - player
+
+
+def try_move(s, player, die, o, d):
+    """a7 / Q6, the reference's order of checks: -> (message, the state afterwards -- unchanged where the move is refused)"""
+    sign = 1 if player == 0 else -1
+    bar_origin = 0 if player == 0 else 25
+    if s[24 + player] > 0:
+        valid = o == bar_origin
+    else:
+        valid = 1 <= o <= 24 and s[o - 1] * sign > 0
+    if not valid:
+        return MESSAGES[1], list(s)                           # (out-of-range origins end here: message 2 is never given)
+    if not 0 <= d <= 25:
+        return MESSAGES[3], list(s)
+    if d in (0, 25):                                          # Q6: either end, any die, no look at the rest of the board
+        if o in (0, 25):
+            return MESSAGES[7], list(s)
+        t = list(s)
+        t[26 + player] += 1
+        t[o - 1] -= sign
+        return "", t
+    if (d - o) * sign < 0:
+        return MESSAGES[4], list(s)
+    if die != abs(d - o):
+        return MESSAGES[5], list(s)
+    if s[d - 1] * sign < -1:
+        return MESSAGES[6], list(s)
+    return "", apply_move(s, player, o, d)

@@ -247,7 +247,9 @@ def test_oracle_vs_compiled_reference_on_arbitrary_boards(golden_dir):
     against the UNMODIFIED reference -- its answers on these boards are fixture G10 (tests/golden/make_golden_g10.py,
     from the reference compiled into oracle/_ref), and wherever that module is present it is asked as well.  The bar counts
     stay 0 here.  (The binding has no setter for them, but hits through setGameBoard + tryMove reach every pair of bar counts:
-    tests/rule_cases.py, fixture G11 and tests/test_rule_cases_cpu.py hold the oracle to the reference on bars 0..15.)"""
+    tests/rule_cases.py, fixture G11 and tests/test_rule_cases_cpu.py hold the oracle to the reference on bars 0..15.  The end of
+    the game -- overruns with the opponent inside the mover's home, wins mid-turn, tryMove's refusals and its unchecked bear-off
+    branch -- is tests/endgame_cases.py, fixture G12 and tests/test_endgame_cases_cpu.py.)"""
     import importlib.util
     import sys
     from helpers import random_boards
