@@ -339,17 +339,15 @@ class VecGame:
         flags = self._flags(roll, auto_reset, no_flip, only_player, slot) | (WANT_INDEX if want_index else 0)
         if plies not in (2, 3):
             raise ValueError("plies must be 2 or 3")
-        self._search_plies = 2
         if plies == 3:
             _capi.check(self._lib.bgamd_env_step_search3(self._h, flags, int(top_k), float("inf") if margin is None else float(margin),
                                                          int(deep_k), float(deep_margin), int(reply_top_k), float(reply_margin), _stream()),
                         "step_search3")
-            self._search_plies = 3
         elif margin is None:
             _capi.check(self._lib.bgamd_env_step_search(self._h, flags, int(top_k), _stream()), "step_search")
         else:
             _capi.check(self._lib.bgamd_env_step_search_filtered(self._h, flags, int(top_k), float(margin), _stream()), "step_search_filtered")
-        self._search_k = int(top_k)
+        self._search_k, self._search_plies = int(top_k), int(plies)      # (of the last step that was accepted: a refused one changes no read)
 
     def search_info(self):
         """Host values of the last search step of either kind (bgamd_env_search_info; synchronises): [lanes that had a move, lanes
@@ -577,6 +575,13 @@ class VecGame:
         _capi.check(self._lib.bgamd_env_rollout_info(self._h, h), "rollout_info")
         return list(h)
 
+    def scratch_info(self):
+        """Lanes of the internal envs as they stand (bgamd_env_scratch_info; host values, no launch): [the search's scratch env, the
+        rollouts' trial env, the 3-ply step's mid env], 0 where there is none yet."""
+        h = (C.c_int64 * 3)()
+        _capi.check(self._lib.bgamd_env_scratch_info(self._h, h), "scratch_info")
+        return list(h)
+
     def last_choice(self):
         ch, cnt = self._buf((self.n,), torch.int32), self._buf((self.n,), torch.int32)
         sq, ln = self._buf((self.n, 4, 2), torch.int8), self._buf((self.n,), torch.int32)
@@ -636,7 +641,8 @@ class VecGame:
     def legal_moves(self, player, die):
         p = self._dev(player, torch.int32, (self.n,))
         d = self._dev(die, torch.int32, (self.n,))
-        n, pairs = self._buf((self.n,), torch.int32), self._buf((self.n, 26, 2), torch.int8)
+        # (the kernel writes a lane's first n pairs: the slots past them are zero, not whatever the allocator handed out)
+        n, pairs = self._buf((self.n,), torch.int32), torch.zeros((self.n, 26, 2), dtype=torch.int8, device=self.device)
         _capi.check(self._lib.bgamd_env_legal_moves(self._h, _ptr(p), _ptr(d), _ptr(n), _ptr(pairs), _stream()), "legal_moves")
         torch.cuda.current_stream().synchronize()
         return n, pairs

@@ -111,6 +111,7 @@ SYMBOLS = [
     ("bgamd_env_kernel_choice", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("bgamd_env_time_kernels", C.c_int, [_P, C.c_int]),
     ("bgamd_env_kernel_times", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("bgamd_env_scratch_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("bgamd_pack_rows", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("bgamd_td_create", C.c_int, [C.POINTER(_P), C.c_int64, C.c_int]),
     ("bgamd_td_destroy", C.c_int, [_P]),

@@ -2922,6 +2922,16 @@ int bgamd_pack_rows(const int32_t *d_states28, const int32_t *d_turn, int64_t n,
     return BGAMD_OK;
 }
 
+// host code only: the lanes of the internal envs as they stand (scratch_env keeps one that is large enough), nothing is launched
+int bgamd_env_scratch_info(bgamd_env *env, int64_t h_out[3])
+{
+    if (!env || !h_out) return BGAMD_E_INVALID;
+    h_out[0] = env->scratch ? (int64_t)env->scratch->v.n : 0;
+    h_out[1] = env->rscratch ? (int64_t)env->rscratch->v.n : 0;
+    h_out[2] = env->mid ? (int64_t)env->mid->v.n : 0;
+    return BGAMD_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------- TD(lambda) learner -------------------------------------------

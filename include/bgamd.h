@@ -16,6 +16,12 @@
  *   - a state is int32[28] = [board24 (+P1/-P2), bar1, bar2, off1, off2]   (game.hpp:16-28);
  *     |count| <= 15.  turn: 0 = PLAYER1, 1 = PLAYER2 (player.hpp:14-18).
  *   - one host thread drives one env; one env lives on one device.
+ *   - history rule: the outputs of a call are a function of its arguments and of the env's documented state -- lanes (boards, side
+ *     to move), dice, ply and episode, seed, the weights of both slots, the settings in force (logs, rollout policy, cube, kernel
+ *     timing) and the counters.  They do not depend on which calls came before, at which sizes, or whether those calls succeeded:
+ *     the internal envs and the buffers an env grows on first use are kept between calls, and nothing may be read from them that
+ *     the call at hand did not write.  A read call (`*_read`, `*_info`, bgamd_env_last_choice) either returns what its own call
+ *     left, bit for bit, however many other calls came in between, or is refused with its documented code.
  */
 #ifndef BGAMD_H
 #define BGAMD_H
@@ -757,6 +763,11 @@ const char *bgamd_build_flags(void);
 int bgamd_env_kernel_choice(bgamd_env *env, int32_t h_out[4]);
 int bgamd_env_time_kernels(bgamd_env *env, int enable);
 int bgamd_env_kernel_times(bgamd_env *env, double h_ms[8], uint64_t h_launches[8]);
+/* The internal envs as they stand: h_out = lanes of the env that scores the virtual roots of the 2-ply search, the move analysis, the
+ * pre-roll evaluation and the rollouts' luck pass (kept while it has at least the lanes a call wants), of the rollouts' trial env
+ * (exactly the last rollout's lanes) and of the 3-ply step's mid env (kept like the first); 0 where there is none yet.  Host values,
+ * nothing is launched.  For tests of the history rule above: no result may depend on these numbers. */
+int bgamd_env_scratch_info(bgamd_env *env, int64_t h_out[3]);
 
 /* states (28 ints, reference getGameBoard layout) + turn -> 32-byte rows, the trajectory log's format */
 int bgamd_pack_rows(const int32_t *d_states28, const int32_t *d_turn, int64_t n, void *d_rows, void *stream);
