@@ -7,6 +7,7 @@
 // This is the ONE place where the rollout's sizing rules and their constants live.
 #pragma once
 #include "../../include/bgamd.h"         // the flags and the error codes
+#include "bg_search_plan.h"              // SEARCH_CHUNK, search_lanes: the scratch env of the 2-ply trials and of the luck pass
 
 namespace bg {
 
@@ -22,12 +23,7 @@ constexpr int ROLLOUT_ROLLS = 21;        // rolls per position of the pre-roll e
 // turns the done counter may stand still beyond the kernels' own limit (RO_TURN_LIMIT, bg_rollout.h) before the loop gives up
 constexpr long long ROLLOUT_STALL_SLACK = 64;
 
-// ---- what the 2-ply search, the pre-roll evaluation and the rollouts share ----
-// Virtual lanes per scoring pass: the search's scratch env has at most this many lanes (a 131 072-lane env: ~3.4 GB).  Every virtual
-// lane is scored on its own, so no result depends on it.
-constexpr long long SEARCH_CHUNK = 131072;
-// the lanes env->scratch needs for n_virtual virtual lanes: rounded up to 256, at most SEARCH_CHUNK
-inline long long search_lanes(long long n_virtual) { return n_virtual < SEARCH_CHUNK ? ((n_virtual + 255) / 256) * 256 : SEARCH_CHUNK; }
+// (SEARCH_CHUNK, the virtual lanes per scoring pass, and search_lanes: bg_search_plan.h)
 
 // the arguments of a call that decide anything, and the env's sticky settings
 struct RolloutRequest {

@@ -45,6 +45,7 @@ constexpr bool EXPERIMENTAL_BUILD = false;
 #include "bg_fit.h"
 #include "bg_schedule.h"
 #include "bg_step_plan.h"
+#include "bg_search_plan.h"
 #include "bg_rollout_plan.h"
 #include "bg_movegen.h"
 #include "bg_staged.h"
@@ -734,6 +735,19 @@ static int net_tables_alloc(DevMem &mem, NetTables &t)
 #undef BOTH
 }
 
+// What the env remembers of its last search step: the read and info calls (bgamd_env_search_read / _info, bgamd_env_search3_read /
+// _info) test it.  One assignment clears the record when a search call of any kind begins, one fills it when a step has succeeded: an
+// analysis, a failed step and a mid env's searches leave every read refusing.
+struct SearchResult {
+    int k = -1;                            // K of the step (-1: none yet, or the last call failed or was no step)
+    uint32_t min_searched = 1;             // the least kept count of a searched lane (bgamd_env_search_info)
+    hipStream_t stream = nullptr;          // the step's stream: the info calls count on it
+    bool deep = false;                     // it was a 3-ply step (bgamd_env_search3_read / _info)
+    bool info_read = false, info3_read = false;            // the host copies below have been read
+    int64_t info[4] = {0, 0, 0, 0};
+    int64_t info3[6] = {0, 0, 0, 0, 0, 0};
+};
+
 // 2-ply search (bgamd_env_step_search, bg_search.h)
 struct SearchState {
     uint32_t *cnt = nullptr, *off = nullptr, *fill = nullptr, *kept = nullptr, *koff = nullptr, *max = nullptr;  // per game (+1)
@@ -743,37 +757,23 @@ struct SearchState {
     uint32_t *c_key = nullptr;
     float *c_v1 = nullptr, *c_v2 = nullptr, *c_rval = nullptr;     // c_rval [c_cap][21]
     long long c_cap = 0;
-    int k = -1;                            // K of the last search step (-1: none yet)
     // the filtered step (bg_filter.h): skept [n] = kept of the searched lanes (kept >= 2, else 0), soff [n + 1] its scan, vmap [c_cap] the
-    // searched candidates' places in the candidate list; bgamd_env_search_info: d_info [4], the least kept count of a searched lane and
-    // the stream of the last search step, the host copy once it has been read
+    // searched candidates' places in the candidate list; bgamd_env_search_info: d_info [4]
     uint32_t *skept = nullptr, *soff = nullptr, *vmap = nullptr;
     unsigned long long *d_info = nullptr;
-    uint32_t min_searched = 1;
-    hipStream_t stream = nullptr;
-    bool info_read = false;
-    int64_t info[4] = {0, 0, 0, 0};
     // the 3-ply step (bg_search3.h), allocated by the first one: dkept [n] = |L2| of the lanes searched deeper (else 0), doff [n + 1] its
     // scan; per candidate [d_cap] c_d3 (rank in L2 or -1), c_v3, dmap (the deep list), r3 [d_cap][21] the mid roots' values; d_info3 [6],
-    // d_l3 the count of level-3 roots.  deep: the last search step was a 3-ply one (bgamd_env_search3_read / _info)
+    // d_l3 the count of level-3 roots
     uint32_t *dkept = nullptr, *doff = nullptr, *dmap = nullptr;
     int32_t *c_d3 = nullptr;
     float *c_v3 = nullptr, *r3 = nullptr;
     unsigned long long *d_info3 = nullptr, *d_l3 = nullptr;
     long long d_cap = 0;
     float *pass_v1 = nullptr;              // a MID env's: [n] the value srch_collect_kernel forms per lane, the pass reply's v1
-    bool deep = false, info3_read = false;
-    int64_t info3[6] = {0, 0, 0, 0, 0, 0};
+    SearchResult last;
 };
 
-// what bgamd_env_step_search3 adds to the filtered step's arguments
-struct Search3Params {
-    int deep_k;
-    float deep_margin;
-    int reply_top_k;
-    float reply_margin;
-};
-// a search of the 3-ply step's mid env (search_stages): the mid lanes are mid roots v0 .. of r3; roots counts the level-3 virtual roots
+// a search of the 3-ply step's mid env (SearchKind::MID): the mid lanes are mid roots v0 .. of r3; roots counts the level-3 virtual roots
 struct Search3Mid {
     s3::DeepList deep;
     float *r3;
@@ -830,7 +830,8 @@ struct RolloutState {
     RolloutResult last;
 };
 static_assert(cube::LANE_FINISHED == META_FINISHED && cube::LANE_NONE == RO_NONE && cube::WORD_TRUNC == RO_TRUNC &&
-              cube::WORD_PTS_SHIFT == RO_PTS_SHIFT && cube::ROLLS == SRCH_ROLLS && ROLLOUT_ROLLS == SRCH_ROLLS, "bg_cube.h and bg_rollout_plan.h restate these");
+              cube::WORD_PTS_SHIFT == RO_PTS_SHIFT && cube::ROLLS == SRCH_ROLLS && ROLLOUT_ROLLS == SRCH_ROLLS && SEARCH_ROLLS == SRCH_ROLLS,
+              "bg_cube.h, bg_rollout_plan.h and bg_search_plan.h restate these");
 
 // pre-roll evaluation (bgamd_env_evaluate_preroll, bg_vr.h)
 struct PrerollState {
@@ -877,7 +878,7 @@ struct bgamd_env {
     // and the pre-roll evaluation score, `rscratch` plays the rollout's trials.  Such an env has no tables of its own: its `net` is its parent's.
     bgamd_env *scratch = nullptr, *rscratch = nullptr;
     // the 3-ply step's mid env (bg_search3.h): one lane per (deep candidate, opponent roll), searched with `scratch` lent to it.  Created by
-    // the first 3-ply step, with at most mid_chunk lanes (SEARCH3_CHUNK, or the test hook BGAMD_SEARCH3_CHUNK read then)
+    // the first 3-ply step, with at most mid_chunk lanes (search3_chunk, bg_search_plan.h, of the test hook BGAMD_SEARCH3_CHUNK read then)
     bgamd_env *mid = nullptr;
     long long mid_chunk = 0;
     // [A_WORDS]: the rollout's counters (RoView::ctr), then the word that takes the bad-state bit of intake_positions -- one allocation, a
@@ -1828,7 +1829,7 @@ int bgamd_env_sample_info(bgamd_env *env, int64_t h_out[2])
 }
 
 // ---- what the 2-ply search, the pre-roll evaluation and the rollouts share --------------------------------------------------------
-// (SEARCH_CHUNK, the virtual lanes per scoring pass, and search_lanes: bg_rollout_plan.h)
+// (SEARCH_CHUNK, the virtual lanes per scoring pass, and search_lanes: bg_search_plan.h)
 
 // *which (env->scratch or env->rscratch) ready to use: an env on env's device with want_lanes lanes -- exactly that many (exact), else
 // at least that many -- created, or after a wait for s re-created, when the one at hand does not do.  Leaves env's device current and
@@ -1867,253 +1868,295 @@ static int intake_positions(bgamd_env *env, const int32_t *d_states28, const int
     return (h & ERRF_STATE) ? BGAMD_E_STATE : BGAMD_OK;
 }
 
-// ---- 2-ply expectimax (bg_search.h) and the move analysis built on it (bg_analysis.h) ------------------------------------------------
-// d_played NULL: the search step.  Else the analysis of the played afterstates d_played [n][28]: the same stages with the played row
-// matched and forced into the kept set, and in place of the choice and the apply launch the per-lane results and their summary.
-// margin NULL: every candidate of the top_k is searched, as ever.  Else the filtered step (bg_filter.h, search step only): the margin
-// rule in the selection, no virtual root for a lane that keeps one candidate, and scoring passes for the list's real length.
-// deep (search step, filtered): the 3-ply step (bg_search3.h) -- between the filtered step's reduce and the apply, search3_deep searches
-// the deep set one ply further and rewrites best[g] of the lanes it searched.  mid (filtered, no apply): the search of that step's mid env
-// -- the pass reply, every kept reply searched, the best V2 of every mid lane into mid->r3.  With both NULL the launches are what they
-// were before either existed.
-static int search3_deep(bgamd_env *env, int slot, const Search3Params &p, hipStream_t s);
-static int search_stages(bgamd_env *env, int flags, int top_k, const int32_t *d_played, const float *margin, hipStream_t s,
-                         const Search3Params *deep = nullptr, const Search3Mid *mid = nullptr)
+// ---- 2-ply expectimax (bg_search.h), its filtered and 3-ply steps (bg_filter.h, bg_search3.h), the move analysis (bg_analysis.h) ------
+namespace {
+// the request of a search of env: the call's kind and first arguments, and what the env has been set to
+SearchRequest search_request(const bgamd_env *env, SearchKind kind, int flags, int top_k, float margin = 0.0f)
 {
-    if (env->v.traj || env->ring_rows) return BGAMD_E_INVALID;       // a search step logs nothing: refused rather than a hole in a log
-    // ... into those two.  Its own log (bgamd_env_set_search_log) is written by the search step alone; the analysis applies nothing and
-    // ignores it.  With auto-reset a lane's next game would write over its last one.
-    const bool logged = env->slog.rows && !d_played;
-    if (logged && (flags & BGAMD_AUTO_RESET)) return BGAMD_E_INVALID;
-    if (!env->net.has_weights[(flags & BGAMD_WEIGHTS_SLOT1) ? 1 : 0]) return BGAMD_E_NOWEIGHTS;
-    const long long n = env->v.n;
-    SearchState &se = env->srch;
-    AnalysisState &an = env->ana;
-    int rc;
-    if (d_played) {
-        an.ready = false;
-        AnaView &v = an.v;                             // all or none: summary != NULL says that every buffer is there
-        if (!an.summary && (rc = env->mem.alloc_group({BG_BUF(v.status, n * 4), BG_BUF(v.distinct, n * 4), BG_BUF(v.rank1, n * 4), BG_BUF(v.rank2, n * 4),
-                BG_BUF(v.v1_played, n * 4), BG_BUF(v.v1_best, n * 4), BG_BUF(v.v2_played, n * 4), BG_BUF(v.v2_best, n * 4), BG_BUF(v.error, n * 4),
-                BG_BUF(v.best, n * 32), BG_BUF(v.ppos, n * 4), BG_BUF(v.pslot, n * 4), BG_BUF(an.summary, ANA_SUMMARY * 8)}))) return rc;
-    }
-    if (!se.cnt) {                                     // all or none: cnt != NULL says that every buffer is there
-        const size_t per_game = (size_t)(n + 1) * 4, per_row = (size_t)env->sv.cap_rows * 4;
-        if ((rc = env->mem.alloc_group({BG_BUF(se.cnt, per_game), BG_BUF(se.off, per_game), BG_BUF(se.fill, per_game), BG_BUF(se.kept, per_game),
-                                        BG_BUF(se.koff, per_game), BG_BUF(se.skept, per_game), BG_BUF(se.soff, per_game),
-                                        BG_BUF(se.max, 8), BG_BUF(se.d_info, 4 * 8), BG_BUF(se.grp, per_row), BG_BUF(se.rank, per_row)})))
+    SearchRequest q{};
+    q.kind = kind; q.flags = flags; q.top_k = top_k; q.margin = margin;
+    q.n = env->v.n; q.cap_rows = env->sv.cap_rows;
+    q.logs_steps = env->v.traj || env->ring_rows;
+    q.has_search_log = env->slog.rows != nullptr;
+    q.has_weights[0] = env->net.has_weights[0]; q.has_weights[1] = env->net.has_weights[1];
+    return q;
+}
+
+// `inner` (a rollout's trial env, a 3-ply step's mid env) searched with owner's scratch env lent to it for the virtual roots: everything is
+// stream-ordered, and a second env of up to SEARCH_CHUNK lanes would buy nothing.  No device is made current: owner's call has done that.
+int search_lent(bgamd_env *owner, bgamd_env *inner, SearchKind kind, int flags, int top_k, float margin, const Search3Mid *mid, hipStream_t s);
+
+// One search call after search_plan has decided it (bg_search_plan.h, plain C++, checked without a GPU: refusal, the select / fan-out /
+// reduce rule, the read-back, the sizes): what the call kept in locals, and its stages in their order.  The step kinds end with the
+// greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice); the analysis and a mid env's search apply nothing.
+struct SearchCall {
+    bgamd_env *env;
+    const SearchPlan &p;
+    hipStream_t s;
+    const int32_t *d_played;               // ANALYSIS: the played afterstates [n][28]
+    const Search3Mid *mid;                 // MID: the mid roots this env's lanes are, and where their values go
+    SearchState &se;                       // env->srch
+    AnalysisState &an;                     // env->ana
+    long long n;                           // env->v.n
+    SearchSized z{};                       // known from list_lengths() on
+    const uint2 *info = nullptr;           // the scored rows (from select() on)
+    const uint4 *rows = nullptr;
+
+    SearchCall(bgamd_env *e, const SearchPlan &plan, hipStream_t stream, const int32_t *played, const Search3Mid *m)
+        : env(e), p(plan), s(stream), d_played(played), mid(m), se(e->srch), an(e->ana), n(e->v.n) {}
+
+    int run()
+    {
+        se.last = SearchResult{};                          // until this call has succeeded as a step, every read refuses
+        if (p.ending == SearchEnding::ANALYSIS) an.ready = false;
+        int rc;
+        if ((rc = buffers()) || (rc = score_roots()) || (rc = select()) || (rc = list_lengths()) || (rc = emit()) || (rc = score_replies()))
             return rc;
+        switch (p.ending) {
+        case SearchEnding::ANALYSIS: return end_analysis();
+        case SearchEnding::MID: return end_mid();
+        default: return end_step();
+        }
     }
-    auto grow_candidates = [&](long long need) {       // (at least 1 024 rows once there is one)
-        return env->mem.grow(need > 0 && need < 1024 ? 1024 : need, se.c_cap,
-                             {BG_BUF(se.c_rows, 32), BG_BUF(se.c_key, 4), BG_BUF(se.c_v1, 4), BG_BUF(se.c_v2, 4),
-                              BG_BUF(se.c_rval, 4 * SRCH_ROLLS), BG_BUF(se.vmap, 4)});
-    };
-    // bound on the kept candidates (top_k = 0: read back below); the analysis keeps the played one beside the top_k
-    long long n_cand = top_k > 0 && !margin ? n * (long long)(top_k + (d_played ? 1 : 0)) : 0;
-    if (n_cand > 0 && (rc = grow_candidates(n_cand))) return rc;
-    se.k = -1;
-    se.deep = false;
-
+    int grow_candidates(long long rows_needed)
+    {
+        return env->mem.grow(rows_needed, se.c_cap, {BG_BUF(se.c_rows, 32), BG_BUF(se.c_key, 4), BG_BUF(se.c_v1, 4), BG_BUF(se.c_v2, 4),
+                                                     BG_BUF(se.c_rval, 4 * SRCH_ROLLS), BG_BUF(se.vmap, 4)});
+    }
+    int buffers()
+    {
+        DevMem &mem = env->mem;
+        int rc;
+        if (p.ending == SearchEnding::ANALYSIS && !an.summary) {           // all or none: summary != NULL says that every buffer is there
+            AnaView &v = an.v;
+            const long long w = p.ana_word_bytes;
+            if ((rc = mem.alloc_group({BG_BUF(v.status, w), BG_BUF(v.distinct, w), BG_BUF(v.rank1, w), BG_BUF(v.rank2, w), BG_BUF(v.v1_played, w),
+                    BG_BUF(v.v1_best, w), BG_BUF(v.v2_played, w), BG_BUF(v.v2_best, w), BG_BUF(v.error, w), BG_BUF(v.best, p.ana_state_bytes),
+                    BG_BUF(v.ppos, w), BG_BUF(v.pslot, w), BG_BUF(an.summary, ANA_SUMMARY * 8)}))) return rc;
+        }
+        if (!se.cnt) {                                     // all or none: cnt != NULL says that every buffer is there
+            const long long per_game = p.per_game_bytes, per_row = p.per_row_bytes;
+            if ((rc = mem.alloc_group({BG_BUF(se.cnt, per_game), BG_BUF(se.off, per_game), BG_BUF(se.fill, per_game), BG_BUF(se.kept, per_game),
+                                       BG_BUF(se.koff, per_game), BG_BUF(se.skept, per_game), BG_BUF(se.soff, per_game),
+                                       BG_BUF(se.max, 8), BG_BUF(se.d_info, 4 * 8), BG_BUF(se.grp, per_row), BG_BUF(se.rank, per_row)})))
+                return rc;
+        }
+        return grow_candidates(p.cand_presize);            // (0: the list's length is read back first)
+    }
     // stage A: the greedy step's roots, expansion and incremental value net, no apply
-    GreedyRun run;
-    if ((rc = run.score(env, flags, s))) return rc;
-
-    // stage B: group by game, select, list the kept candidates
-    const unsigned long long *tops = env->sv.tops;
-    const long long bb = env->sv.b_base, cap_rows = env->sv.cap_rows;
-    const uint2 *info = env->sv.u_info;
-    const uint4 *rows = env->sv.u_rows;
-    const dim3 rgrid((unsigned)(env->n_cu * 8));
-    HIPCHK(hipMemsetAsync(se.cnt, 0, (size_t)n * 4, s));
-    HIPCHK(hipMemsetAsync(se.fill, 0, (size_t)n * 4, s));
-    hipLaunchKernelGGL(srch_count_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, se.cnt);
-    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.cnt, se.off, n, (uint32_t *)nullptr);
-    hipLaunchKernelGGL(srch_scatter_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, (const uint32_t *)se.off, se.fill, se.grp);
-    const uint32_t k_lim = top_k > 0 ? (uint32_t)top_k : 0xFFFFFFFFu;
-    if (d_played) {
-        hipLaunchKernelGGL(ana_match_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, env->v, flags, d_played, (const uint32_t *)se.cnt,
-                           (const uint32_t *)se.off, (const uint32_t *)se.grp, rows, info, an.v);
-        hipLaunchKernelGGL(ana_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
-                           (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept, an.v);
-    } else if (margin)
-        hipLaunchKernelGGL(flt_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
-                           (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, *margin, se.rank, se.kept, se.skept);
-    else
-        hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
-                           (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, k_lim, se.rank, se.kept);
-    if (mid)                                           // a mid lane without rows keeps its pass reply
-        s3::reply_fix(s, n, mid->v0, mid->deep, (const uint32_t *)se.cnt, se.kept);
-    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.kept, se.koff, n, se.max);
-    int K = top_k;
-    long long n_searched = 0;                          // filtered step: the searched candidates (those of the lanes that kept >= 2)
-    const bool singletons_skipped = margin && !mid;    // (the mid env searches every kept reply: its searched list is its candidate list)
-    if (singletons_skipped)
-        hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.skept, se.soff, n, (uint32_t *)nullptr);
-    if (margin || top_k == 0) {                        // the list's length is not known here (filtered, or every distinct afterstate): it is read
-        uint32_t h[3] = {0, 0, 0};                     // back, with the searched list's when filtered (the one synchronisation)
-        HIPCHK(hipMemcpyAsync(&h[0], se.koff + n, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&h[1], se.max, 4, hipMemcpyDeviceToHost, s));
-        if (singletons_skipped) HIPCHK(hipMemcpyAsync(&h[2], se.soff + n, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        n_cand = h[0]; n_searched = h[2];
-        if (top_k == 0) K = (int)h[1];
-        if ((rc = grow_candidates(n_cand))) return rc;
+    int score_roots()
+    {
+        GreedyRun run;
+        return run.score(env, p.flags, s);
     }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(srch_emit_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
-                       (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, (const int32_t *)se.rank,
-                       (const uint32_t *)se.koff, se.c_rows, se.c_key, se.c_v1);
-    if (mid && n_cand > 0) {                           // the pass replies: v1 as srch_collect_kernel forms the value of a lane without a move
-        if (!se.pass_v1 && (rc = env->mem.alloc(BG_BUF(se.pass_v1, (size_t)n * 4)))) return rc;
-        hipLaunchKernelGGL(srch_collect_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, (const unsigned long long *)env->sv.best,
-                           (const float *)env->sv.root_hidden, env->net.w2(run.slot), env->net.b2(run.slot), 0ll, se.pass_v1);
-        s3::pass_emit(s, n, mid->v0, mid->deep, (const uint32_t *)se.cnt, (const uint32_t *)se.koff, (const float *)se.pass_v1, se.c_rows,
-                      se.c_key, se.c_v1);
+    // stage B: group by game, select
+    int select()
+    {
+        const unsigned long long *tops = env->sv.tops;
+        const long long bb = env->sv.b_base, cap_rows = env->sv.cap_rows;
+        info = env->sv.u_info;
+        rows = env->sv.u_rows;
+        const dim3 rgrid((unsigned)(env->n_cu * 8));
+        HIPCHK(hipMemsetAsync(se.cnt, 0, (size_t)n * 4, s));
+        HIPCHK(hipMemsetAsync(se.fill, 0, (size_t)n * 4, s));
+        hipLaunchKernelGGL(srch_count_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, se.cnt);
+        hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.cnt, se.off, n, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(srch_scatter_kernel, rgrid, dim3(SRCH_NT), 0, s, tops, bb, cap_rows, info, (const uint32_t *)se.off, se.fill, se.grp);
+        if (p.match_played)
+            hipLaunchKernelGGL(ana_match_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, env->v, p.flags, d_played, (const uint32_t *)se.cnt,
+                               (const uint32_t *)se.off, (const uint32_t *)se.grp, rows, info, an.v);
+        switch (p.select) {
+        case SearchSelect::ANALYSIS:
+            hipLaunchKernelGGL(ana_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                               (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, p.k_lim, se.rank, se.kept, an.v);
+            break;
+        case SearchSelect::MARGIN:
+            hipLaunchKernelGGL(flt_select_kernel<64>, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                               (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, p.k_lim, p.margin, se.rank, se.kept, se.skept);
+            break;
+        case SearchSelect::PLAIN:
+            hipLaunchKernelGGL(srch_select_kernel, dim3((unsigned)n), dim3(64), 0, s, n, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                               (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, p.k_lim, se.rank, se.kept);
+            break;
+        }
+        if (p.pass_replies)                                // a mid lane without rows keeps its pass reply
+            s3::reply_fix(s, n, mid->v0, mid->deep, (const uint32_t *)se.cnt, se.kept);
+        return BGAMD_OK;
     }
-
-    // stage C: one virtual lane per (candidate, opponent roll), scored on the scratch env
-    const long long n_virtual = (singletons_skipped ? n_searched : n_cand) * SRCH_ROLLS;
-    if (singletons_skipped && n_virtual > 0) {
-        hipLaunchKernelGGL(flt_vmap_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
-                           (const uint32_t *)se.koff, (const uint32_t *)se.soff, se.vmap);
-        if ((rc = scratch_env(env, &env->scratch, search_lanes(n_virtual), false, 0, s))) return rc;
+    // ... list the kept candidates (and the searched ones), and size what follows: read back, or known from the plan
+    int list_lengths()
+    {
+        hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.kept, se.koff, n, se.max);
+        if (p.skip_singletons)
+            hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.skept, se.soff, n, (uint32_t *)nullptr);
+        uint32_t h[3] = {0, 0, 0};
+        if (p.read_back) {                                 // (the one synchronisation)
+            HIPCHK(hipMemcpyAsync(&h[0], se.koff + n, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(&h[1], se.max, 4, hipMemcpyDeviceToHost, s));
+            if (p.read_searched) HIPCHK(hipMemcpyAsync(&h[2], se.soff + n, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        z = search_sized(p, h[0], h[1], h[2]);
+        int rc;
+        if (p.read_back && (rc = grow_candidates(z.cand_rows))) return rc;
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    }
+    int emit()
+    {
+        hipLaunchKernelGGL(srch_emit_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint32_t *)se.cnt, (const uint32_t *)se.off,
+                           (const uint32_t *)se.grp, rows, info, (const float *)env->v.values, (const int32_t *)se.rank,
+                           (const uint32_t *)se.koff, se.c_rows, se.c_key, se.c_v1);
+        if (p.pass_replies && z.n_cand > 0) {              // the pass replies: v1 as srch_collect_kernel forms the value of a lane without a move
+            int rc;
+            if (!se.pass_v1 && (rc = env->mem.alloc(BG_BUF(se.pass_v1, (size_t)n * 4)))) return rc;
+            hipLaunchKernelGGL(srch_collect_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, (const unsigned long long *)env->sv.best,
+                               (const float *)env->sv.root_hidden, env->net.w2(p.slot), env->net.b2(p.slot), 0ll, se.pass_v1);
+            s3::pass_emit(s, n, mid->v0, mid->deep, (const uint32_t *)se.cnt, (const uint32_t *)se.koff, (const float *)se.pass_v1, se.c_rows,
+                          se.c_key, se.c_v1);
+        }
+        return BGAMD_OK;
+    }
+    // stage C: one virtual lane per (searched candidate, opponent roll), scored on the scratch env
+    int score_replies()
+    {
+        if (z.n_virtual == 0) return BGAMD_OK;
+        const bool mapped = p.fanout == SearchFanout::MAPPED;
+        if (mapped)
+            hipLaunchKernelGGL(flt_vmap_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                               (const uint32_t *)se.koff, (const uint32_t *)se.soff, se.vmap);
+        if (const int rc = scratch_env(env, &env->scratch, z.scratch_lanes, false, 0, s)) return rc;
         const auto fanout = [&](const EnvView &lanes, long long v0) {
-            hipLaunchKernelGGL(flt_fanout_kernel<SRCH_NT>, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.soff + n),
-                               (const uint32_t *)se.vmap, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
+            if (mapped)
+                hipLaunchKernelGGL(flt_fanout_kernel<SRCH_NT>, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.soff + n),
+                                   (const uint32_t *)se.vmap, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
+            else
+                hipLaunchKernelGGL(srch_fanout_kernel, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.koff + n),
+                                   (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
         };
-        if ((rc = score_virtual_lanes(env, run.slot, n_virtual, fanout, se.c_rval, s))) return rc;
-    } else if (n_virtual > 0) {
-        if ((rc = scratch_env(env, &env->scratch, search_lanes(n_virtual), false, 0, s))) return rc;
-        const auto fanout = [&](const EnvView &lanes, long long v0) {
-            hipLaunchKernelGGL(srch_fanout_kernel, grid1(lanes.n, SRCH_NT), dim3(SRCH_NT), 0, s, lanes, v0, (const uint32_t *)(se.koff + n),
-                               (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
-        };
-        if ((rc = score_virtual_lanes(env, run.slot, n_virtual, fanout, se.c_rval, s))) return rc;
+        return score_virtual_lanes(env, p.slot, z.n_virtual, fanout, se.c_rval, s);
     }
-
-    // stage D of the analysis: V2, the best and the played candidate's place, the summary -- nothing is applied
-    unsigned long long *scratch_err = env->scratch ? &env->scratch->v.counters[C_ERR] : (unsigned long long *)nullptr;
-    if (d_played) {
+    unsigned long long *scratch_err() const { return env->scratch ? &env->scratch->v.counters[C_ERR] : (unsigned long long *)nullptr; }
+    // stage D of the analysis: V2, the best and the played candidate's place, the summary
+    int end_analysis()
+    {
         hipLaunchKernelGGL(ana_reduce_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
                            (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
-                           (const float *)se.c_rval, se.c_v2, an.v, &env->v.counters[C_ERR], scratch_err);
+                           (const float *)se.c_rval, se.c_v2, an.v, &env->v.counters[C_ERR], scratch_err());
         hipLaunchKernelGGL(ana_summary_kernel<ANA_SUM_NT>, dim3(1), dim3(ANA_SUM_NT), 0, s, env->v, an.v, an.summary);
         HIPCHK(hipGetLastError());
         an.ready = true;
         return BGAMD_OK;
     }
-    if (mid) {                                         // the mid env's stage D: the best searched reply of every mid lane, nothing applied
+    // stage D of a mid env: the best searched reply of every mid lane into the 3-ply step's r3
+    int end_mid()
+    {
         s3::r3_reduce(s, n, mid->v0, mid->deep, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.c_key,
-                      (const float *)se.c_v1, (const float *)se.c_rval, se.c_v2, mid->r3, mid->roots, &env->v.counters[C_ERR], scratch_err);
+                      (const float *)se.c_v1, (const float *)se.c_rval, se.c_v2, mid->r3, mid->roots, &env->v.counters[C_ERR], scratch_err());
         HIPCHK(hipGetLastError());
         return BGAMD_OK;
     }
-    // stage D: V2, choice, and the greedy step's own apply (terminal check, flip / auto-reset, counters, last_choice)
-    if (margin)
-        hipLaunchKernelGGL(flt_reduce_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
-                           (const uint32_t *)se.koff, (const uint32_t *)se.soff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key,
-                           (const float *)se.c_v1, (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err);
-    else
-        hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
-                           (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
-                           (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err);
-    if (logged)
-        hipLaunchKernelGGL(srch_log_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, flags, (const uint4 *)env->sv.root_rows,
-                           (const unsigned long long *)env->sv.best, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows,
-                           (const uint32_t *)se.c_key, (const float *)se.c_v1, (const float *)se.c_v2, margin ? 2u : 1u, env->slog);
-    if (deep && (rc = search3_deep(env, run.slot, *deep, s))) return rc;
-    const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
-    hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, flags, 0.0f);
-    HIPCHK(hipGetLastError());
-    se.k = K;
-    se.min_searched = margin ? 2u : 1u;
-    se.stream = s;
-    se.info_read = false;
-    se.deep = deep != nullptr;
-    se.info3_read = false;
-    return BGAMD_OK;
-}
-
-// ---- the 3-ply step's deep level (bg_search3.h) ---------------------------------------------------------------------------------------
-// Mid lanes per chunk: the mid env has at most this many lanes (~1.8 GB at 65 536, its search buffers included).  A chunk costs ~1.5 ms
-// beside its scoring passes (its launches and its one synchronisation): at 16 384 lanes per chunk a 16 384-lane step took 74 ms, at
-// 65 536 it takes 49 ms (profiles/search3.txt).  Every mid lane is searched on its own, so no result depends on it; BGAMD_SEARCH3_CHUNK
-// (a multiple of 256) overrides it for the tests.
-constexpr long long SEARCH3_CHUNK = 65536;
-
-// env holds a filtered step's kept lists, V2 and best[g].  Selects the deep set of every searched lane, searches its (candidate, opponent
-// roll) mid lanes on env->mid a chunk at a time -- env->scratch lent to it for the virtual roots, as the 2-ply rollouts lend it -- and
-// leaves best[g] of the lanes searched deeper as their V3 choice.  Synchronises s once for the deep list's length and once per mid chunk.
-static int search3_deep(bgamd_env *env, int slot, const Search3Params &p, hipStream_t s)
-{
-    SearchState &se = env->srch;
-    const long long n = env->v.n;
-    int rc;
-    if (!se.dkept) {                                   // all or none: dkept != NULL says that every buffer is there
-        const size_t per_game = (size_t)(n + 1) * 4;
-        if ((rc = env->mem.alloc_group({BG_BUF(se.dkept, per_game), BG_BUF(se.doff, per_game), BG_BUF(se.d_info3, 6 * 8), BG_BUF(se.d_l3, 8)})))
-            return rc;
+    // stage D of a step: V2 and the choice, the log, the 3-ply step's deep level, the apply -- and the env remembers the step
+    int end_step()
+    {
+        if (p.ending == SearchEnding::FILTERED)
+            hipLaunchKernelGGL(flt_reduce_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                               (const uint32_t *)se.koff, (const uint32_t *)se.soff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key,
+                               (const float *)se.c_v1, (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err());
+        else
+            hipLaunchKernelGGL(srch_reduce_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept,
+                               (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1,
+                               (const float *)se.c_rval, se.c_v2, env->sv.best, &env->v.counters[C_ERR], scratch_err());
+        if (p.logged)
+            hipLaunchKernelGGL(srch_log_kernel<SRCH_NT>, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, env->v, p.flags, (const uint4 *)env->sv.root_rows,
+                               (const unsigned long long *)env->sv.best, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows,
+                               (const uint32_t *)se.c_key, (const float *)se.c_v1, (const float *)se.c_v2, p.min_searched, env->slog);
+        int rc;
+        if (p.deep && (rc = deep_level())) return rc;
+        const ExploreView xv{env->rv.tasks, env->rv.task_count, env->rv.task_off, env->rv.task_n};
+        hipLaunchKernelGGL(apply_kernel, grid1(n, LANE_NT), dim3(LANE_NT), 0, s, env->v, env->sv, xv, p.flags, 0.0f);
+        HIPCHK(hipGetLastError());
+        se.last = SearchResult{z.K, p.min_searched, s, p.deep};
+        return BGAMD_OK;
     }
-    if ((rc = env->mem.grow(se.c_cap, se.d_cap, {BG_BUF(se.c_d3, 4), BG_BUF(se.c_v3, 4), BG_BUF(se.dmap, 4), BG_BUF(se.r3, 4 * SRCH_ROLLS)})))
-        return rc;
-    HIPCHK(hipMemsetAsync(se.d_l3, 0, 8, s));
-    s3::deep_select(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key,
-                    (const float *)se.c_v2, p.deep_k > 0 ? (uint32_t)p.deep_k : 0xFFFFFFFFu, p.deep_margin, se.c_d3, se.dkept);
-    hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.dkept, se.doff, n, (uint32_t *)nullptr);
-    uint32_t n_deep = 0;
-    HIPCHK(hipMemcpyAsync(&n_deep, se.doff + n, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    if (n_deep == 0) return BGAMD_OK;                  // no lane is searched deeper: the filtered step's choices stand
-    s3::deep_map(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept, (const uint32_t *)se.doff,
-                 (const int32_t *)se.c_d3, se.dmap);
-
-    const long long n_mid = (long long)n_deep * SRCH_ROLLS;
-    if (!env->mid_chunk) {
-        env->mid_chunk = SEARCH3_CHUNK;
-        if (const char *h = getenv("BGAMD_SEARCH3_CHUNK")) {
-            const long long c = atoll(h);
-            if (c >= 256 && c % 256 == 0) env->mid_chunk = c;
+    // The 3-ply step's deep level (bg_search3.h): env holds a filtered step's kept lists, V2 and best[g].  Selects the deep set of every
+    // searched lane, searches its (candidate, opponent roll) mid lanes on env->mid a chunk at a time -- env->scratch lent to it -- and
+    // leaves best[g] of the lanes searched deeper as their V3 choice.  Synchronises s once for the deep list's length and once per chunk.
+    int deep_level()
+    {
+        int rc;
+        if (!se.dkept) {                                   // all or none: dkept != NULL says that every buffer is there
+            const long long per_game = p.deep_game_bytes;
+            if ((rc = env->mem.alloc_group({BG_BUF(se.dkept, per_game), BG_BUF(se.doff, per_game), BG_BUF(se.d_info3, 6 * 8), BG_BUF(se.d_l3, 8)})))
+                return rc;
         }
+        if ((rc = env->mem.grow(se.c_cap, se.d_cap, {BG_BUF(se.c_d3, 4), BG_BUF(se.c_v3, 4), BG_BUF(se.dmap, 4), BG_BUF(se.r3, 4 * SRCH_ROLLS)})))
+            return rc;
+        HIPCHK(hipMemsetAsync(se.d_l3, 0, 8, s));
+        s3::deep_select(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key,
+                        (const float *)se.c_v2, p.deep_k_lim, p.deep_margin, se.c_d3, se.dkept);
+        hipLaunchKernelGGL(srch_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)se.dkept, se.doff, n, (uint32_t *)nullptr);
+        uint32_t n_deep = 0;
+        HIPCHK(hipMemcpyAsync(&n_deep, se.doff + n, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        if (n_deep && !env->mid_chunk) env->mid_chunk = search3_chunk(getenv("BGAMD_SEARCH3_CHUNK"));
+        const DeepPlan d = deep_plan(n_deep, env->mid_chunk);
+        if (d.none) return BGAMD_OK;                       // no lane is searched deeper: the filtered step's choices stand
+        s3::deep_map(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept, (const uint32_t *)se.doff,
+                     (const int32_t *)se.c_d3, se.dmap);
+        if ((rc = scratch_env(env, &env->mid, d.mid_lanes, false, 0, s))) return rc;
+        bgamd_env *me = env->mid;
+        for (long long v0 = 0; v0 < d.n_mid; v0 += me->v.n) {
+            hipLaunchKernelGGL(flt_fanout_kernel<SRCH_NT>, grid1(me->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, me->v, v0, (const uint32_t *)(se.doff + n),
+                               (const uint32_t *)se.dmap, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
+            const Search3Mid out{{se.doff + n, se.dmap, se.c_rows, se.c_key}, se.r3, v0, se.d_l3};
+            if ((rc = search_lent(env, me, SearchKind::MID, p.slot ? BGAMD_WEIGHTS_SLOT1 : 0, p.reply_top_k, p.reply_margin, &out, s))) return rc;
+        }
+        s3::v3_reduce(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept, (const uint32_t *)se.doff,
+                      (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1, (const int32_t *)se.c_d3, (const float *)se.r3,
+                      se.c_v3, env->sv.best, &env->v.counters[C_ERR], &me->v.counters[C_ERR]);
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
     }
-    const long long want = n_mid < env->mid_chunk ? ((n_mid + 255) / 256) * 256 : env->mid_chunk;
-    if ((rc = scratch_env(env, &env->mid, want, false, 0, s))) return rc;
-    bgamd_env *mid = env->mid;
-    for (long long v0 = 0; v0 < n_mid; v0 += mid->v.n) {
-        hipLaunchKernelGGL(flt_fanout_kernel<SRCH_NT>, grid1(mid->v.n, SRCH_NT), dim3(SRCH_NT), 0, s, mid->v, v0, (const uint32_t *)(se.doff + n),
-                           (const uint32_t *)se.dmap, (const uint4 *)se.c_rows, (const uint32_t *)se.c_key);
-        const Search3Mid out{{se.doff + n, se.dmap, se.c_rows, se.c_key}, se.r3, v0, se.d_l3};
-        mid->scratch = env->scratch;
-        rc = search_stages(mid, slot ? BGAMD_WEIGHTS_SLOT1 : 0, p.reply_top_k, nullptr, &p.reply_margin, s, nullptr, &out);
-        env->scratch = mid->scratch;                   // (re-created if it had to grow)
-        mid->scratch = nullptr;
-        if (rc) return rc;
-    }
-    s3::v3_reduce(s, n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept, (const uint32_t *)se.doff,
-                  (const uint4 *)se.c_rows, (const uint32_t *)se.c_key, (const float *)se.c_v1, (const int32_t *)se.c_d3, (const float *)se.r3,
-                  se.c_v3, env->sv.best, &env->v.counters[C_ERR], &mid->v.counters[C_ERR]);
-    HIPCHK(hipGetLastError());
-    return BGAMD_OK;
+};
+
+int search_lent(bgamd_env *owner, bgamd_env *inner, SearchKind kind, int flags, int top_k, float margin, const Search3Mid *mid, hipStream_t s)
+{
+    const SearchPlan p = search_plan(search_request(inner, kind, flags, top_k, margin));
+    if (p.rc) return p.rc;
+    inner->scratch = owner->scratch;
+    const int rc = SearchCall(inner, p, s, nullptr, mid).run();
+    owner->scratch = inner->scratch;                       // (re-created if it had to grow)
+    inner->scratch = nullptr;
+    return rc;
 }
+
+// a search entry point's call on the caller's env: refused with the plan's code, or run
+int search_entry(bgamd_env *env, const SearchRequest &q, const int32_t *d_played, void *stream)
+{
+    const SearchPlan p = search_plan(q);
+    if (p.rc) return p.rc;
+    HIPCHK(hipSetDevice(env->device));
+    return SearchCall(env, p, (hipStream_t)stream, d_played, nullptr).run();
+}
+}  // namespace
 
 int bgamd_env_step_search3(bgamd_env *env, int flags, int top_k, float margin, int deep_k, float deep_margin, int reply_top_k,
                            float reply_margin, void *stream)
 {
-    if (!env || top_k < 0 || deep_k < 0 || reply_top_k < 0 || !(margin >= 0.0f) || !(deep_margin >= 0.0f) || !(reply_margin >= 0.0f))
-        return BGAMD_E_INVALID;                                          // (a NaN margin fails its comparison)
-    if (env->slog.rows) return BGAMD_E_INVALID;                          // 3-ply targets are not logged: refused, not written half-right
-    HIPCHK(hipSetDevice(env->device));
-    const Search3Params p{deep_k, deep_margin, reply_top_k, reply_margin};
-    return search_stages(env, flags, top_k, nullptr, &margin, (hipStream_t)stream, &p);
+    if (!env) return BGAMD_E_INVALID;
+    SearchRequest q = search_request(env, SearchKind::THREE_PLY, flags, top_k, margin);
+    q.deep_k = deep_k; q.deep_margin = deep_margin; q.reply_top_k = reply_top_k; q.reply_margin = reply_margin;
+    return search_entry(env, q, nullptr, stream);
 }
 
 int bgamd_env_search3_read(bgamd_env *env, float *d_v3, int32_t *d_depth, void *stream)
 {
     ENV_GUARD(env);
     const SearchState &se = env->srch;
-    if (se.k < 0 || !se.deep) return BGAMD_E_INVALID;
-    const long long n = env->v.n, K = se.k;
+    if (se.last.k < 0 || !se.last.deep) return BGAMD_E_INVALID;
+    const long long n = env->v.n, K = se.last.k;
     if (K > 0 && (d_v3 || d_depth))
         s3::read((hipStream_t)stream, n, (int)K, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept,
                  (const int32_t *)se.c_d3, (const float *)se.c_v3, d_v3, d_depth);
@@ -2126,32 +2169,30 @@ int bgamd_env_search3_info(bgamd_env *env, int64_t h_out[6])
 {
     ENV_GUARD(env);
     SearchState &se = env->srch;
-    if (!h_out || se.k < 0 || !se.deep) return BGAMD_E_INVALID;
-    if (!se.info3_read) {
+    if (!h_out || se.last.k < 0 || !se.last.deep) return BGAMD_E_INVALID;
+    if (!se.last.info3_read) {
         unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-        s3::info(se.stream, (long long)env->v.n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept,
+        s3::info(se.last.stream, (long long)env->v.n, (const uint32_t *)se.kept, (const uint32_t *)se.koff, (const uint32_t *)se.dkept,
                  (const uint32_t *)se.c_key, (const int32_t *)se.c_d3, (const unsigned long long *)se.d_l3, se.d_info3);
-        HIPCHK(hipMemcpyAsync(h, se.d_info3, 6 * 8, hipMemcpyDeviceToHost, se.stream));
-        HIPCHK(hipStreamSynchronize(se.stream));
-        for (int q = 0; q < 6; ++q) se.info3[q] = (int64_t)h[q];
-        se.info3_read = true;
+        HIPCHK(hipMemcpyAsync(h, se.d_info3, 6 * 8, hipMemcpyDeviceToHost, se.last.stream));
+        HIPCHK(hipStreamSynchronize(se.last.stream));
+        for (int q = 0; q < 6; ++q) se.last.info3[q] = (int64_t)h[q];
+        se.last.info3_read = true;
     }
-    for (int q = 0; q < 6; ++q) h_out[q] = se.info3[q];
+    for (int q = 0; q < 6; ++q) h_out[q] = se.last.info3[q];
     return BGAMD_OK;
 }
 
 int bgamd_env_step_search(bgamd_env *env, int flags, int top_k, void *stream)
 {
-    if (!env || top_k < 0) return BGAMD_E_INVALID;
-    HIPCHK(hipSetDevice(env->device));
-    return search_stages(env, flags, top_k, nullptr, nullptr, (hipStream_t)stream);
+    if (!env) return BGAMD_E_INVALID;
+    return search_entry(env, search_request(env, SearchKind::STEP, flags, top_k), nullptr, stream);
 }
 
 int bgamd_env_step_search_filtered(bgamd_env *env, int flags, int top_k, float margin, void *stream)
 {
-    if (!env || top_k < 0 || !(margin >= 0.0f)) return BGAMD_E_INVALID;      // (a NaN margin fails the comparison)
-    HIPCHK(hipSetDevice(env->device));
-    return search_stages(env, flags, top_k, nullptr, &margin, (hipStream_t)stream);
+    if (!env) return BGAMD_E_INVALID;
+    return search_entry(env, search_request(env, SearchKind::FILTERED, flags, top_k, margin), nullptr, stream);
 }
 
 // The counts are taken when they are asked for, on the stream of the step they describe: a search step launches nothing for them.
@@ -2159,26 +2200,27 @@ int bgamd_env_search_info(bgamd_env *env, int64_t h_out[4])
 {
     ENV_GUARD(env);
     SearchState &se = env->srch;
-    if (!h_out || se.k < 0) return BGAMD_E_INVALID;
-    if (!se.info_read) {
+    if (!h_out || se.last.k < 0) return BGAMD_E_INVALID;
+    if (!se.last.info_read) {
         unsigned long long h[4] = {0, 0, 0, 0};
-        hipLaunchKernelGGL(flt_info_kernel<1024>, dim3(1), dim3(1024), 0, se.stream, (long long)env->v.n, (const uint32_t *)se.kept,
-                           (const uint32_t *)se.koff, (const uint32_t *)se.c_key, se.min_searched, se.d_info);
-        HIPCHK(hipMemcpyAsync(h, se.d_info, 4 * 8, hipMemcpyDeviceToHost, se.stream));
-        HIPCHK(hipStreamSynchronize(se.stream));
-        for (int q = 0; q < 4; ++q) se.info[q] = (int64_t)h[q];
-        se.info_read = true;
+        hipLaunchKernelGGL(flt_info_kernel<1024>, dim3(1), dim3(1024), 0, se.last.stream, (long long)env->v.n, (const uint32_t *)se.kept,
+                           (const uint32_t *)se.koff, (const uint32_t *)se.c_key, se.last.min_searched, se.d_info);
+        HIPCHK(hipMemcpyAsync(h, se.d_info, 4 * 8, hipMemcpyDeviceToHost, se.last.stream));
+        HIPCHK(hipStreamSynchronize(se.last.stream));
+        for (int q = 0; q < 4; ++q) se.last.info[q] = (int64_t)h[q];
+        se.last.info_read = true;
     }
-    for (int q = 0; q < 4; ++q) h_out[q] = se.info[q];
+    for (int q = 0; q < 4; ++q) h_out[q] = se.last.info[q];
     return BGAMD_OK;
 }
 
 // ---- move analysis (bg_analysis.h) -------------------------------------------------------------------------------------------------
 int bgamd_env_analyze_moves(bgamd_env *env, int flags, int top_k, const int32_t *d_played28, void *stream)
 {
-    if (!env || !d_played28 || top_k < 0 || (flags & ~(BGAMD_ONLY_P1 | BGAMD_ONLY_P2 | BGAMD_WEIGHTS_SLOT1))) return BGAMD_E_INVALID;
-    HIPCHK(hipSetDevice(env->device));
-    return search_stages(env, flags, top_k, d_played28, nullptr, (hipStream_t)stream);
+    if (!env) return BGAMD_E_INVALID;
+    SearchRequest q = search_request(env, SearchKind::ANALYSIS, flags, top_k);
+    q.has_played = d_played28 != nullptr;
+    return search_entry(env, q, d_played28, stream);
 }
 
 int bgamd_env_analysis_read(bgamd_env *env, int32_t *d_status, int32_t *d_distinct, int32_t *d_rank1, int32_t *d_rank2,
@@ -2200,9 +2242,9 @@ int bgamd_env_search_read(bgamd_env *env, int32_t *d_states28, float *d_v1, floa
 {
     ENV_GUARD(env);
     const SearchState &se = env->srch;
-    if (se.k < 0) return BGAMD_E_INVALID;
+    if (se.last.k < 0) return BGAMD_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const long long n = env->v.n, K = se.k;
+    const long long n = env->v.n, K = se.last.k;
     if (d_kept) hipLaunchKernelGGL(srch_kept_kernel, grid1(n, SRCH_NT), dim3(SRCH_NT), 0, s, n, (const uint32_t *)se.kept, d_kept);
     if (K > 0 && (d_states28 || d_v1 || d_v2))
         hipLaunchKernelGGL(srch_read_kernel, grid1(n * K, SRCH_NT), dim3(SRCH_NT), 0, s, n, (int)K, (const uint32_t *)se.kept,
@@ -2329,11 +2371,7 @@ struct RolloutCall {
     }
     int search_turn()
     {
-        sc->scratch = env->scratch;
-        const int e = search_stages(sc, p.run_flags, env->ro_top_k, nullptr, &env->ro_margin, s);
-        env->scratch = sc->scratch;                    // (re-created if it had to grow)
-        sc->scratch = nullptr;
-        return e;
+        return search_lent(env, sc, SearchKind::FILTERED, p.run_flags, env->ro_top_k, env->ro_margin, nullptr, s);
     }
     // rotation: the first turn of every (position, ordered pair) as one greedy step with injected dice, L virtual lanes at a time
     int fan()

@@ -80,7 +80,7 @@ int run_singles(Handle &x)                             // env_allocate: one allo
     return 0;
 }
 
-int first_use_group(Handle &x)                         // search_stages: `if (!se.cnt)`, then eleven buffers
+int first_use_group(Handle &x)                         // SearchCall::buffers: `if (!se.cnt)`, then eleven buffers
 {
     int *(&p)[11] = x.group;
     if (p[0]) return 0;

@@ -9,7 +9,7 @@ import nets as N
 import search_model as M
 import search_ref as S
 
-SEARCH_CHUNK = 131072          # csrc/bg_rollout_plan.h: virtual lanes per scoring pass
+SEARCH_CHUNK = 131072          # csrc/bg_search_plan.h: virtual lanes per scoring pass
 DYADIC_SEED = 7
 
 

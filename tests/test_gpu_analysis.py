@@ -1,4 +1,4 @@
-"""The move analysis on the MI355X (bgamd_env_analyze_moves / bgamd_env_analysis_read: csrc/bg_analysis.h and search_stages in
+"""The move analysis on the MI355X (bgamd_env_analyze_moves / bgamd_env_analysis_read: csrc/bg_analysis.h and SearchCall in
 csrc/bgamd.hip), lane by lane and bit for bit against the exact model tests/analysis_model.py fed with the device's own float32 values:
 one full-width search per net on the 1 500 G10 boards (test_gpu_search_rules' cached runs) gives v1 and V2 of every distinct afterstate
 by reference index; every analysis below -- any top_k, any played candidate, one to four scoring passes -- must report exactly what
