@@ -14,6 +14,7 @@ from the reference, which replays games one after another.
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import numpy as np
@@ -237,6 +238,33 @@ class TDLambdaLearner:
                 "fc2.bias": b2.clone()}
 
 
+# How the update of a device learner's training step reaches the weights:
+LOCAL = "local"          # the library applies it itself: bgamd_td_replay, bgamd_td_fit_step without an update buffer.  No collective.
+LIBRARY = "library"      # the learner's own RCCL communicator all-reduces it: bgamd_td_replay_allreduce, bgamd_td_fit_step_allreduce
+TORCH = "torch"          # Python drives it: bgamd_td_step -> dist.all_reduce -> bgamd_td_apply, step by step
+Route = collections.namedtuple("Route", "distributed kind world")
+
+
+def replay_route(world: int, group_up: bool, has_comm: bool, force_collective: bool, torch_collective: bool, split_apply: bool = False):
+    """The ONE decision of how DeviceTDLambdaLearner issues a replay or a fit step, from plain facts (no GPU, no process group needed):
+    world = the group's size (1 without a process group), group_up = torch.distributed is initialised, has_comm = the learner has a
+    communicator (init_collective), force_collective = BGAMD_FORCE_COLLECTIVE=1, torch_collective = BGAMD_TD_TORCH_COLLECTIVE=1,
+    split_apply = the caller asked for the step / apply route.  -> Route(distributed, kind, world):
+    distributed: a collective goes with every training step -- more than one rank, or BGAMD_FORCE_COLLECTIVE=1 on a world of one that has
+        something to issue it with (what tools/train_dist_step.py and the world-of-one tests measure: the cost of the call itself);
+    kind: LOCAL unless distributed or split_apply; LIBRARY where a distributed replay finds a communicator and BGAMD_TD_TORCH_COLLECTIVE
+        does not hold it back (split_apply does not: the library's route is a split one already); TORCH otherwise -- on one rank
+        (split_apply alone) it issues no collective, and with a communicator but no process group its first collective raises."""
+    distributed = world > 1 or (force_collective and (group_up or has_comm))
+    if not distributed and not split_apply:
+        kind = LOCAL
+    elif distributed and has_comm and not torch_collective:
+        kind = LIBRARY
+    else:
+        kind = TORCH
+    return Route(distributed, kind, world)
+
+
 class DeviceTDLambdaLearner:
     """The same lock-step TD(λ) replay as TDLambdaLearner.replay, in hand-written HIP kernels (csrc/bg_learner.h,
     C ABI bgamd_td_*): it reads the env's 32-byte trajectory rows directly (no [T, G, 198] tensor), keeps the
@@ -290,19 +318,11 @@ class DeviceTDLambdaLearner:
         chk(lib.bgamd_td_comm_init(self._h, buf, rank, world), "td_comm_init")
         self._comm = (rank, world)
 
-    @staticmethod
-    def _world(group):
-        return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-
-    def _distributed(self, group):
-        """the replay issues a collective per training step: more than one rank, or BGAMD_FORCE_COLLECTIVE=1 on a world of one (what
-        tools/train_dist_step.py and the world-1 test measure: the cost of the call with the communicator present)"""
-        forced = os.environ.get("BGAMD_FORCE_COLLECTIVE") == "1"
-        return self._world(group) > 1 or (forced and ((dist.is_available() and dist.is_initialized()) or getattr(self, "_comm", None) is not None))
-
-    def _in_library(self, distributed):
-        """the library's own collective serves this replay: the learner has a communicator and the replay is a distributed one"""
-        return distributed and getattr(self, "_comm", None) is not None and os.environ.get("BGAMD_TD_TORCH_COLLECTIVE") != "1"
+    def _route(self, group, split_apply=False):
+        """replay_route of this learner, this group and the environment as they stand at the call"""
+        up = dist.is_available() and dist.is_initialized()
+        return replay_route(dist.get_world_size(group) if up else 1, up, getattr(self, "_comm", None) is not None,
+                            os.environ.get("BGAMD_FORCE_COLLECTIVE") == "1", os.environ.get("BGAMD_TD_TORCH_COLLECTIVE") == "1", split_apply)
 
     def set_delay(self, delay: int):
         """delay = 1: streamed replays through 512 ... 4 096 slots apply the update of step t one step late, and a training step is one launch
@@ -373,12 +393,12 @@ class DeviceTDLambdaLearner:
             raise ValueError("one target per row")
         a = float(self.learning_rate if alpha is None else alpha) * float(batch_scale)
         pr, py = (self._p(rows), self._p(y)) if n else (None, None)
-        distributed = self._distributed(group)
-        if not distributed:
+        kind = self._route(group).kind
+        if kind == LOCAL:
             chk(lib.bgamd_td_fit_step(self._h, pr, py, n, a, None, self._s()), "td_fit_step")
-        elif self._in_library(True):
+        elif kind == LIBRARY:
             chk(lib.bgamd_td_fit_step_allreduce(self._h, pr, py, n, a, self._s()), "td_fit_step_allreduce")
-        else:
+        else:                                                        # (one step, one collective: nothing to share with _issue's loop)
             upd = torch.empty(25601, dtype=torch.float32, device=self.device)
             chk(lib.bgamd_td_fit_step(self._h, pr, py, n, a, self._p(upd), self._s()), "td_fit_step")
             dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)
@@ -476,24 +496,20 @@ class DeviceTDLambdaLearner:
             raise ValueError("a game is longer than the trajectory log")
         sl, order = torch.sort(lengths, descending=True, stable=True)
         n_games = int((sl > 0).sum().item())
-        # BGAMD_FORCE_COLLECTIVE=1: issue the per-step all-reduce on a group of ONE rank too (tools/train_dist_step.py measures what the
-        # collective's launch costs a training step with the RCCL communicator present; more ranks are the driver's to launch)
-        distributed = self._distributed(group)
+        route = self._route(group, split_apply)
         if slots and slots > 0:
-            return self._replay_stream(rows, T, n, lengths, won, order[:n_games], sl[:n_games], int(slots), group, distributed,
-                                       batch_scale, split_apply)
+            return self._replay_stream(rows, T, n, lengths, won, int(slots), group, route, batch_scale)
         n_sub = 1
         if sub_round and sub_round > 0:
             n_sub = max(1, -(-n_games // int(sub_round)))
-        if distributed and self._world(group) > 1:              # every rank runs the same number of sub-rounds
+        if route.world > 1:                                     # every rank runs the same number of sub-rounds
             ns = torch.tensor([n_sub], dtype=torch.int64, device=self.device)
             dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)
             n_sub = int(ns.item())
         sq_tot, cnt_tot = 0.0, 0
         for c in range(n_sub):
             o = order[:n_games][c::n_sub].to(torch.int32).contiguous()
-            sq, cnt = self._replay_order(rows, T, n, lengths, won, o, sl[:n_games][c::n_sub], group, distributed,
-                                         batch_scale, split_apply)
+            sq, cnt = self._replay_order(rows, T, n, lengths, won, o, sl[:n_games][c::n_sub], group, route, batch_scale)
             sq_tot += sq
             cnt_tot += cnt
         return sq_tot, cnt_tot
@@ -503,7 +519,7 @@ class DeviceTDLambdaLearner:
         game i sits in column game_lane[i] of ring_rows [R, n, 8], its turn k in ring slot (game_start[i] + k) % R, lengths / p1_won are
         per game.  The same schedule, kernels and arithmetic as replay_rows(slots=k): a table with one game per lane starting in slot 0
         IS replay_rows.  Returns (Σ δ², number of (game, step) updates)."""
-        C, lib, chk = self._C, self._lib, self._capi.check
+        lib, chk = self._lib, self._capi.check
         ring_rows = ring_rows.contiguous()
         R, n = int(ring_rows.shape[0]), int(ring_rows.shape[1])
         lane = torch.as_tensor(game_lane, device=self.device).to(torch.int32).contiguous()
@@ -515,101 +531,86 @@ class DeviceTDLambdaLearner:
             raise ValueError("game table columns differ in length")
         if G and int(lengths.max().item()) > R:
             raise ValueError("a game is longer than the ring log")
-        distributed = self._distributed(group)
-        h_len = lengths.cpu().numpy().astype(np.int32, copy=False) if G else np.zeros(1, dtype=np.int32)
-        k = max(1, min(int(slots), self.max_games))
-        h_queue, h_qoff = np.zeros(max(G, 1), dtype=np.int32), np.zeros(k + 1, dtype=np.int32)
-        ng, nst = C.c_int64(), C.c_int64()
-        chk(lib.bgamd_td_stream_schedule(h_len.ctypes.data, G, k, h_queue.ctypes.data, h_qoff.ctypes.data, C.byref(ng), C.byref(nst)),
-            "td_stream_schedule")
-        k = min(k, int(ng.value))
-        n_steps = int(nst.value)
-        queue = torch.from_numpy(h_queue[:max(int(ng.value), 1)]).to(self.device)
-        qoff = torch.from_numpy(h_qoff[:k + 1]).to(self.device)
+        route = self._route(group)
+        k, n_steps, queue, qoff = self._stream_plan(lengths, G, slots)
         if G == 0:                                                   # (a rank without finished games still joins the collectives below)
             lane = start = lengths = torch.zeros(1, dtype=torch.int32, device=self.device)
             won = torch.zeros(1, dtype=torch.uint8, device=self.device)
         self._keep = (ring_rows, lane, start, lengths, won, queue, qoff)
         chk(lib.bgamd_td_begin_stream_games(self._h, self._p(ring_rows), R, n, self._p(queue), self._p(qoff), k, max(G, 1), self._p(lane),
                                             self._p(start), self._p(lengths), self._p(won), self._s()), "td_begin_stream_games")
+        return self._issue(n_steps, [k] * n_steps, route, group, batch_scale, max_reduce=route.world > 1, step_past_own=False,
+                           sum_reduce=True)
+
+    def _stream_plan(self, lengths, n, slots):
+        """The schedule of a streamed replay, from the library (host code: a copy of the lengths goes down, the two index arrays come up):
+        lengths int32 [n] per lane or per game (n = 0: a rank with nothing to replay) -> (k slots in use, n_steps = the longest slot's
+        turns, queue, qoff on the device).  No game with a turn: k = 0 and n_steps = 0 (csrc/bg_schedule.h: n_steps is the largest slot
+        total, and no slot is dealt a game), so n_steps is also what the rank owns of a replay it shares with others."""
+        C = self._C
+        h_len = lengths.cpu().numpy().astype(np.int32, copy=False) if n else np.zeros(1, dtype=np.int32)
+        k = max(1, min(int(slots), self.max_games))
+        h_queue, h_qoff = np.zeros(max(n, 1), dtype=np.int32), np.zeros(k + 1, dtype=np.int32)
+        ng, nst = C.c_int64(), C.c_int64()
+        self._capi.check(self._lib.bgamd_td_stream_schedule(h_len.ctypes.data, n, k, h_queue.ctypes.data, h_qoff.ctypes.data, C.byref(ng),
+                                                            C.byref(nst)), "td_stream_schedule")
+        k = min(k, int(ng.value))
+        queue = torch.from_numpy(h_queue[:max(int(ng.value), 1)]).to(self.device)
+        qoff = torch.from_numpy(h_qoff[:k + 1]).to(self.device)
+        return k, int(nst.value), queue, qoff
+
+    def _replay_stream(self, rows, T, n, lengths, won, slots, group, route, batch_scale):
+        """Streamed replay (bgamd_td_begin_stream) of the lanes with a length."""
+        k, n_steps, queue, qoff = self._stream_plan(lengths, n, slots)
+        self._keep = (rows, lengths, won, queue, qoff)
+        self._capi.check(self._lib.bgamd_td_begin_stream(self._h, self._p(rows), T, n, self._p(queue), self._p(qoff), k,
+                                                         self._p(lengths), self._p(won), self._s()), "td_begin_stream")
+        return self._issue(n_steps, [k] * n_steps, route, group, batch_scale, max_reduce=route.distributed, step_past_own=True,
+                           sum_reduce=route.distributed)
+
+    def _issue(self, n_steps, n_active, route, group, batch_scale, *, max_reduce, step_past_own, sum_reduce):
+        """Issues the training steps of the replay just begun -- this rank's own n_steps, n_active[t] slots at step t -- the way `route`
+        says, reads the closing statistics and lets go of the buffers the caller put in _keep before it began.
+        -> (Σ δ², number of (game, step) updates).
+        LOCAL: one bgamd_td_replay.  LIBRARY: the step count MAX-reduced over a world of more than one, then one bgamd_td_replay_allreduce
+        with the own steps handed down.  TORCH: a loop of bgamd_td_step (or a zeroed update where the rank has no step) -> all-reduce ->
+        bgamd_td_apply, in which the three entry points differ in three places (NOTEBOOK.md, "one replay route"); each is an argument:"""
+        # max_reduce:    TORCH MAX-reduces the step count.  replay_rows, lock-step and streamed: route.distributed (a forced world of
+        #                one reduces too); replay_games: route.world > 1
+        # step_past_own: TORCH calls bgamd_td_step at every step once the rank has any, also past its own last one, where every slot's
+        #                queue is used up.  replay_rows streamed: True; replay_rows lock-step, replay_games: False (the update is zeroed)
+        # sum_reduce:    TORCH all-reduces every step's update.  replay_rows, lock-step and streamed: route.distributed (split_apply on
+        #                its own issues none); replay_games: True (no split_apply there: its TORCH is always a distributed one)
+        C, lib, chk = self._C, self._lib, self._capi.check
         alpha = float(self.learning_rate) * float(batch_scale)
         lam = float(self.lambda_decay)
-        if not distributed:
-            arr = (C.c_int64 * max(n_steps, 1))(*([k] * n_steps))
+        arr = (C.c_int64 * max(n_steps, 1))(*n_active)
+        if route.kind == LOCAL:
             chk(lib.bgamd_td_replay(self._h, n_steps, arr, alpha, lam, self._s()), "td_replay")
         else:
             ns = torch.tensor([n_steps], dtype=torch.int64, device=self.device)
-            if self._world(group) > 1:
-                dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)
-            if self._in_library(True):
-                own = n_steps if G else 0
-                arr = (C.c_int64 * max(own, 1))(*([k] * own))
-                chk(lib.bgamd_td_replay_allreduce(self._h, int(ns.item()), arr, own, alpha, lam, self._s()), "td_replay_allreduce")
+            if route.world > 1 if route.kind == LIBRARY else max_reduce:
+                dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)      # every rank issues the same collectives
+            if route.kind == LIBRARY:
+                chk(lib.bgamd_td_replay_allreduce(self._h, int(ns.item()), arr, n_steps, alpha, lam, self._s()), "td_replay_allreduce")
             else:
                 upd = torch.zeros(25601, dtype=torch.float32, device=self.device)
                 for t in range(int(ns.item())):
-                    if G and t < n_steps:
-                        chk(lib.bgamd_td_step(self._h, t, k, alpha, lam, self._p(upd), self._s()), "td_step")
+                    if t < n_steps or (step_past_own and n_steps):
+                        chk(lib.bgamd_td_step(self._h, t, n_active[min(t, n_steps - 1)], alpha, lam, self._p(upd), self._s()), "td_step")
                     else:
                         upd.zero_()
-                    dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)
+                    if sum_reduce:
+                        dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)  # the ONE collective per training step
                     chk(lib.bgamd_td_apply(self._h, self._p(upd), self._s()), "td_apply")
         sq, cnt = C.c_double(), C.c_int64()
         chk(lib.bgamd_td_stats(self._h, C.byref(sq), C.byref(cnt)), "td_stats")
         self._keep = None
         return float(sq.value), int(cnt.value)
 
-    def _replay_stream(self, rows, T, n, lengths, won, order, sl, slots, group, distributed, batch_scale, split_apply):
-        """Streamed replay (bgamd_td_begin_stream): order = lanes by decreasing length sl."""
-        C, lib, chk = self._C, self._lib, self._capi.check
-        n_games = int(order.numel())
-        # the schedule comes from the library (host code: a copy of the lengths goes down, the two index arrays come up)
-        h_len = lengths.cpu().numpy().astype(np.int32, copy=False)
-        k = max(1, min(int(slots), self.max_games))
-        h_queue, h_qoff = np.zeros(max(n, 1), dtype=np.int32), np.zeros(k + 1, dtype=np.int32)
-        ng, nst = C.c_int64(), C.c_int64()
-        chk(lib.bgamd_td_stream_schedule(h_len.ctypes.data, n, k, h_queue.ctypes.data, h_qoff.ctypes.data, C.byref(ng), C.byref(nst)),
-            "td_stream_schedule")
-        k = min(k, int(ng.value))
-        n_steps = int(nst.value)
-        queue = torch.from_numpy(h_queue[:max(int(ng.value), 1)]).to(self.device)
-        qoff = torch.from_numpy(h_qoff[:k + 1]).to(self.device)
-        self._keep = (rows, lengths, won, queue, qoff)
-        chk(lib.bgamd_td_begin_stream(self._h, self._p(rows), T, n, self._p(queue), self._p(qoff), k,
-                                      self._p(lengths), self._p(won), self._s()), "td_begin_stream")
-        alpha = float(self.learning_rate) * float(batch_scale)
-        lam = float(self.lambda_decay)
-        if not distributed and not split_apply:
-            arr = (C.c_int64 * max(n_steps, 1))(*([k] * n_steps))
-            chk(lib.bgamd_td_replay(self._h, n_steps, arr, alpha, lam, self._s()), "td_replay")
-        elif self._in_library(distributed):
-            ns = torch.tensor([n_steps], dtype=torch.int64, device=self.device)
-            if self._world(group) > 1:
-                dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)      # every rank issues the same collectives
-            own = n_steps if n_games else 0
-            arr = (C.c_int64 * max(own, 1))(*([k] * own))
-            chk(lib.bgamd_td_replay_allreduce(self._h, int(ns.item()), arr, own, alpha, lam, self._s()), "td_replay_allreduce")
-        else:
-            ns = torch.tensor([n_steps], dtype=torch.int64, device=self.device)
-            if distributed:
-                dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)  # every rank issues the same collectives
-            upd = torch.zeros(25601, dtype=torch.float32, device=self.device)
-            for t in range(int(ns.item())):
-                if n_games:
-                    chk(lib.bgamd_td_step(self._h, t, k, alpha, lam, self._p(upd), self._s()), "td_step")
-                else:
-                    upd.zero_()
-                if distributed:
-                    dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)  # the ONE collective per training step
-                chk(lib.bgamd_td_apply(self._h, self._p(upd), self._s()), "td_apply")
-        sq, cnt = C.c_double(), C.c_int64()
-        chk(lib.bgamd_td_stats(self._h, C.byref(sq), C.byref(cnt)), "td_stats")
-        self._keep = None
-        return float(sq.value), int(cnt.value)
-
-    def _replay_order(self, rows, T, n, lengths, won, order, sl, group, distributed, batch_scale, split_apply):
+    def _replay_order(self, rows, T, n, lengths, won, order, sl, group, route, batch_scale):
         """Lock-step replay of the games order[...] (lanes, by decreasing length sl)."""
-        C, lib, chk = self._C, self._lib, self._capi.check
+        lib, chk = self._lib, self._capi.check
         n_games = int(order.numel())
         if n_games > self.max_games:
             raise ValueError(f"{n_games} games > max_games={self.max_games}")
@@ -620,34 +621,8 @@ class DeviceTDLambdaLearner:
         self._keep = (rows, lengths, won, order)
         chk(lib.bgamd_td_begin(self._h, self._p(rows), T, n, self._p(order), n_games, self._p(lengths), self._p(won),
                                self._s()), "td_begin")
-        alpha = float(self.learning_rate) * float(batch_scale)
-        lam = float(self.lambda_decay)
-        if not distributed and not split_apply:
-            arr = (C.c_int64 * max(n_steps, 1))(*n_active)
-            chk(lib.bgamd_td_replay(self._h, n_steps, arr, alpha, lam, self._s()), "td_replay")
-        elif self._in_library(distributed):
-            ns = torch.tensor([n_steps], dtype=torch.int64, device=self.device)
-            if self._world(group) > 1:
-                dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)      # every rank issues the same collectives
-            arr = (C.c_int64 * max(n_steps, 1))(*n_active)
-            chk(lib.bgamd_td_replay_allreduce(self._h, int(ns.item()), arr, n_steps, alpha, lam, self._s()), "td_replay_allreduce")
-        else:
-            ns = torch.tensor([n_steps], dtype=torch.int64, device=self.device)
-            if distributed:
-                dist.all_reduce(ns, op=dist.ReduceOp.MAX, group=group)  # every rank issues the same collectives
-            upd = torch.zeros(25601, dtype=torch.float32, device=self.device)
-            for t in range(int(ns.item())):
-                if t < n_steps:
-                    chk(lib.bgamd_td_step(self._h, t, n_active[t], alpha, lam, self._p(upd), self._s()), "td_step")
-                else:
-                    upd.zero_()
-                if distributed:
-                    dist.all_reduce(upd, op=dist.ReduceOp.SUM, group=group)  # the ONE collective per training step
-                chk(lib.bgamd_td_apply(self._h, self._p(upd), self._s()), "td_apply")
-        sq, cnt = C.c_double(), C.c_int64()
-        chk(lib.bgamd_td_stats(self._h, C.byref(sq), C.byref(cnt)), "td_stats")
-        self._keep = None
-        return float(sq.value), int(cnt.value)
+        return self._issue(n_steps, n_active, route, group, batch_scale, max_reduce=route.distributed, step_past_own=False,
+                           sum_reduce=route.distributed)
 
 
 def _run_policy(env, n_steps, auto_reset, epsilon, temperature, precision):
