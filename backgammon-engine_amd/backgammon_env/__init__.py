@@ -27,10 +27,11 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import (AUTO_RESET, BF16, CUBE_HOLD_TURN0, CUBE_JACOBY, CUBE_ON, F16X2, F32, F32_DENSE, NO_FLIP, ONLY_P1,  # noqa: F401
+from ._capi import (AUTO_RESET, BF16, CUBE_HOLD_TURN0, CUBE_JACOBY, CUBE_ON, F16X2, F32, F32_DENSE, MATCH_ON, NO_FLIP, ONLY_P1,  # noqa: F401
                     ONLY_P2, ROLL, ROLLOUT_ROTATE, ROLLOUT_VR, WANT_INDEX, WEIGHTS_SLOT1, BgamdError)
+from .match import Match, MatchTable  # noqa: F401
 
-__all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "Cube", "BgamdError", "set_seed", "pack_rows", "outcomes"]
+__all__ = ["PlayerType", "Player", "Pieces", "Game", "VecGame", "Cube", "Match", "MatchTable", "BgamdError", "set_seed", "pack_rows", "outcomes"]
 
 
 @dataclasses.dataclass
@@ -422,7 +423,7 @@ class VecGame:
 
     def rollout(self, states28, turn, trials, max_plies=0, rotate=True, seed=20240603, slot=0, position_offset=0, lanes=0,
                 per_trial=False, variance_reduction=False, outcomes=False, plies=1, top_k=4, margin=float("inf"), groups=None,
-                group_offset=0, cube=None):
+                group_offset=0, cube=None, match=None):
         """Monte Carlo rollouts (include/bgamd.h, bgamd_env_rollout): `trials` greedy games from each of the P positions (turn = side to
         move), trial i of position p with the TURN-stream dice of game id (position_offset + p) * trials + i; rotate: the first turn of
         trial i uses ordered dice pair i % 36.  max_plies > 0 stops a trial after that many turns and scores it by the fp32 net.  This
@@ -446,7 +447,15 @@ class VecGame:
         cube_counts [P, 4] (int64: trials PLAYER1 passed, trials PLAYER2 passed, cube turns, trials that ended at max_cube), with
         per_trial trial_cubeful [P, T] (float64), trial_cube [P, T] (int32, the final cube), trial_dropped [P, T] (int32, the turn of
         the drop or -1).  The other outputs are the same as without it.  The cube decides on the luck pass's pre-roll means: cube
-        without variance_reduction is a ValueError."""
+        without variance_reduction is a ValueError.
+        match (a backgammon_env.Match; needs cube=, else ValueError): the cube is handled by the thresholds of each position's match
+        score and the trials are worth match-winning chances (bgamd_env_rollout_match, set for this call and cleared afterwards;
+        the cube's double_at and pass_at are ignored, jacoby is refused) -- also mwc [P], mwc_stderr [P] (float64, PLAYER1's
+        match-winning chance) and match_counts [P, 3] (int64: trials that ended the match for PLAYER1, for PLAYER2, trials in which a
+        decision was withheld by a dead cube), with per_trial trial_mwc [P, T].  The other outputs are the same as without it;
+        cubeful, trial_cube and trial_dropped describe in points the records the match rule produced."""
+        if match is not None and cube is None:
+            raise ValueError("rollout: a match sets the cube's thresholds; pass cube= with match=")
         if cube is not None and not variance_reduction:
             raise ValueError("rollout: the cube decides on the luck pass's pre-roll means; pass variance_reduction=True with cube")
         if groups is not None and int(position_offset) != 0:
@@ -457,7 +466,7 @@ class VecGame:
             _capi.check(self._lib.bgamd_env_rollout_policy(self._h, int(plies), int(top_k), float(margin)), "rollout_policy")
             try:
                 return self.rollout(states28, turn, trials, max_plies, rotate, seed, slot, position_offset, lanes, per_trial,
-                                    variance_reduction, outcomes, groups=groups, group_offset=group_offset, cube=cube)
+                                    variance_reduction, outcomes, groups=groups, group_offset=group_offset, cube=cube, match=match)
             finally:
                 _capi.check(self._lib.bgamd_env_rollout_policy(self._h, 1, 0, 0.0), "rollout_policy")
         st = torch.as_tensor(states28, dtype=torch.int32).to(self.device).contiguous().reshape(-1, 28)
@@ -485,6 +494,9 @@ class VecGame:
                                                          float(c.pass_at), float(c.too_good_at), int(c.max_cube), _ptr(cv), _ptr(co)),
                         "rollout_cube")
         try:
+            if match is not None:
+                a1, a2, ms = (torch.from_numpy(x).to(self.device) for x in match.per_position(P))
+                self._set_match(match.table, match.window_share, a1, a2, ms)
             if groups is None:
                 _capi.check(self._lib.bgamd_env_rollout(self._h, flags, _ptr(st), _ptr(t), P, int(position_offset), T, int(max_plies),
                                                         int(seed) & (2 ** 64 - 1), int(lanes), _ptr(out["mean"]), _ptr(out["stderr"]),
@@ -499,6 +511,8 @@ class VecGame:
         finally:
             if cube is not None:                           # (the setting is sticky in the C ABI; here it lasts for the call, like plies)
                 _capi.check(self._lib.bgamd_env_rollout_cube(self._h, 0, 0.0, 0.0, 0.0, 0, None, None), "rollout_cube")
+            if match is not None:
+                _capi.check(self._lib.bgamd_env_rollout_match(self._h, 0, 0, None, None, 0.0, None, None, None), "rollout_match")
         self._rollout_shape = (P, T)
         if variance_reduction:
             out["vr_mean"], out["vr_stderr"] = self._buf((P,), torch.float64), self._buf((P,), torch.float64)
@@ -510,7 +524,36 @@ class VecGame:
             out.update(self.rollout_outcomes_read(per_trial=per_trial))
         if cube is not None:
             out.update(self.rollout_cube_read(per_trial=per_trial))
+        if match is not None:
+            out.update(self.rollout_match_read(per_trial=per_trial))
         return out
+
+    def _set_match(self, table, window_share, away1, away2, state):
+        """bgamd_env_rollout_match with BGAMD_MATCH_ON: the host tables are copied at the call, the three device tensors are read by the
+        next rollout's intake"""
+        _capi.check(self._lib.bgamd_env_rollout_match(self._h, MATCH_ON, int(table.M), C.c_void_p(table.met.ctypes.data),
+                                                      C.c_void_p(table.met_pc.ctypes.data), float(window_share), _ptr(away1), _ptr(away2),
+                                                      _ptr(state)), "rollout_match")
+
+    def rollout_match_read(self, per_trial=False):
+        """The last rollout's match results (bgamd_env_rollout_match_results; raises unless that rollout had match=) -> dict: mwc [P],
+        mwc_stderr [P], match_counts [P, 3], per_trial: trial_mwc [P, T] -- see rollout(match=)."""
+        P, T = self._rollout_shape
+        out = {"mwc": self._buf((P,), torch.float64), "mwc_stderr": self._buf((P,), torch.float64),
+               "match_counts": self._buf((P, 3), torch.int64)}
+        if per_trial:
+            out["trial_mwc"] = self._buf((P, T), torch.float64)
+        _capi.check(self._lib.bgamd_env_rollout_match_results(self._h, _ptr(out["mwc"]), _ptr(out["mwc_stderr"]), _ptr(out["match_counts"]),
+                                                           _ptr(out.get("trial_mwc")), _stream()), "rollout_match_read")
+        return out
+
+    def rollout_match_thresholds(self, state, cube, a, b):
+        """(double_at, pass_at) of the threshold table of the last match setting, read back from the device
+        (bgamd_env_rollout_match_thresholds): state 0 or 2, cube a power of two below the table's size, a the roller's and b the
+        opponent's points to go; (inf, inf) where no decision is made."""
+        h = (C.c_double * 2)()
+        _capi.check(self._lib.bgamd_env_rollout_match_thresholds(self._h, int(state), int(cube), int(a), int(b), h), "rollout_match_thresholds")
+        return float(h[0]), float(h[1])
 
     def rollout_cube_read(self, per_trial=False):
         """The last rollout's cube results (bgamd_env_rollout_cube_read; raises unless that rollout had cube=) -> dict: cubeful [P],
@@ -547,18 +590,18 @@ class VecGame:
                     "rollout_outcomes_read")
         return out
 
-    PAIRED_WHICH = {"value": 0, "vr": 1, "equity": 2, "cubeful": 3}
+    PAIRED_WHICH = {"value": 0, "vr": 1, "equity": 2, "cubeful": 3, "mwc": 4}
 
     def rollout_paired(self, ref, which="value"):
         """Paired differences of the last rollout (bgamd_env_rollout_paired_read): for each position p and its reference ref[p] (an index
         into that call's positions), mean and standard error of the per-trial differences q_i(p) - q_i(ref[p]) -- q the trial's value
         ("value"), its luck-adjusted value ("vr": the rollout must have had variance_reduction), its equity in points ("equity") or its cubeful equity ("cubeful": the rollout
-        must have had cube=).  Only
+        must have had cube=) or its match-winning chance ("mwc": the rollout must have had match=).  Only
         positions of one dice group share dice: a reference in another group, or out of range, gives NaN for that p; after a rollout
         without groups every ref[p] != p does.  ref[p] = p gives 0.  -> (diff_mean [P], diff_stderr [P]), float64 device tensors;
         stream-ordered."""
         if which not in self.PAIRED_WHICH:
-            raise ValueError("rollout_paired: which is one of 'value', 'vr', 'equity', 'cubeful'")
+            raise ValueError("rollout_paired: which is one of 'value', 'vr', 'equity', 'cubeful', 'mwc'")
         P, _ = self._rollout_shape
         r = torch.as_tensor(ref).to(torch.int64).reshape(-1)
         if r.shape[0] != P:

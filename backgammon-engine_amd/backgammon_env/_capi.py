@@ -19,6 +19,7 @@ ROLL, AUTO_RESET, NO_FLIP, WANT_INDEX, ONLY_P1, ONLY_P2, WEIGHTS_SLOT1 = 1, 2, 4
 ROLLOUT_ROTATE = 128
 ROLLOUT_VR = 256
 CUBE_ON, CUBE_JACOBY, CUBE_HOLD_TURN0 = 1, 2, 4      # bgamd_env_rollout_cube's flags
+MATCH_ON = 1                             # bgamd_env_rollout_match's flag
 OUTCOME_BAD = -2 ** 31                   # BGAMD_OUTCOME_BAD
 F32, BF16, F16X2, F32_DENSE = 0, 1, 2, 3
 
@@ -90,6 +91,9 @@ SYMBOLS = [
     ("bgamd_env_rollout_cube", C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P]),
     ("bgamd_env_rollout_cube_read", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     ("bgamd_env_rollout_cube_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("bgamd_env_rollout_match", C.c_int, [_P, C.c_int, C.c_int64, _P, _P, C.c_double, _P, _P, _P]),
+    ("bgamd_env_rollout_match_results", C.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("bgamd_env_rollout_match_thresholds", C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("bgamd_env_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("bgamd_env_reset_stats", C.c_int, [_P, _P]),
     ("bgamd_env_try_move", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),

@@ -153,7 +153,7 @@ def cube_decision(nd, dt, dp):
 
 
 def cube_action(env, states28, turn, cube_value=1, cube_owner=0, trials=1296, max_plies=0, plies=1, rollout_top_k=4,
-                rollout_margin=float("inf"), seed=20240603, group_offset=0, lanes=0, cube=None):
+                rollout_margin=float("inf"), seed=20240603, group_offset=0, lanes=0, cube=None, match=None):
     """Double or not, take or pass: the cube action of each position by ONE grouped cubeful rollout.
 
     env: a VecGame with weights in slot 0 (its lanes are untouched).  states28 [P, 28] / turn [P]: the positions, `turn` to roll and
@@ -174,7 +174,17 @@ def cube_action(env, states28, turn, cube_value=1, cube_owner=0, trials=1296, ma
                           trials are in none);
          action           one of CUBE_ACTIONS by cube_decision(nd, dt, dp).
        A position whose roller has no access to the cube carries nd (and the cubeless fields) only, with action "no access"; a
-       position that is already over likewise, with action "game over"."""
+       position that is already over likewise, with action "game over".
+
+    match (a backgammon_env.Match, its scores scalars or one per position): the same at a match score (VecGame.rollout(match=...)).
+    nd, dt, dp, diff and their standard errors are then the ROLLER's match-winning chances instead of points -- dp = W(c), the
+    roller's chance after winning the cube's value, from the roller's own row of the table as the thresholds read it (nd and dt
+    of a PLAYER2 roller are 1 - PLAYER1's chance, the payoff being PLAYER1's: on a table that is not complementary the two views
+    differ); diff is the paired dt - nd of the trials' MWC
+    (rollout_paired(which="mwc")) --, cube_decision is applied to them unchanged, and `mwc` is PLAYER1's chance of the no-double
+    copy.  The cube's double_at and pass_at are ignored by the trials (the thresholds follow from the score).  A position in the
+    Crawford game carries nd only with action "Crawford game", one whose cube is dead for the roller (c >= its points to go)
+    likewise with action "dead cube"."""
     from . import Cube
     st = np.asarray(states28.cpu() if hasattr(states28, "cpu") else states28, dtype=np.int32).reshape(-1, 28)
     P = st.shape[0]
@@ -186,6 +196,13 @@ def cube_action(env, states28, turn, cube_value=1, cube_owner=0, trials=1296, ma
         raise ValueError("cube_action: the Jacoby rule counts cube turns inside a trial; the double under analysis is made before it")
     over = (st[:, 26] == 15) | (st[:, 27] == 15)
     access = ((co == 0) | (co == tu + 1)) & ~over
+    label = {}
+    if match is not None:
+        a1, a2, ms = (x.astype(np.int64) for x in match.per_position(P))
+        mine = np.where(tu == 0, a1, a2)
+        for p in np.flatnonzero(access & ((ms == 1) | (cv >= mine))):
+            label[int(p)] = "Crawford game" if ms[p] == 1 else "dead cube"
+        access = access & ~((ms == 1) | (cv >= mine))
     nd_of = list(range(P))
     dt_of = {}
     rows, turns, values, owners, groups = list(range(P)), list(tu), list(cv), list(co), list(range(P))
@@ -193,11 +210,14 @@ def cube_action(env, states28, turn, cube_value=1, cube_owner=0, trials=1296, ma
         dt_of[int(p)] = len(rows)
         rows.append(int(p)); turns.append(tu[p]); values.append(2 * cv[p]); owners.append(2 - tu[p]); groups.append(int(p))
     rule = Cube(rule.double_at, rule.pass_at, rule.too_good_at, rule.max_cube, False, True, np.asarray(values), np.asarray(owners))
+    if match is not None:
+        from .match import Match
+        match = Match(match.table, a1[rows], a2[rows], ms[rows], match.window_share)
     r = env.rollout(st[rows], np.asarray(turns), trials, max_plies=max_plies, rotate=True, seed=seed, lanes=lanes, variance_reduction=True,
                     outcomes=True, plies=plies, top_k=rollout_top_k, margin=rollout_margin, groups=groups, group_offset=group_offset,
-                    cube=rule)
+                    cube=rule, match=match)
     ref = [nd_of[g] for g in groups]                       # every copy against its position's no-double copy
-    dm, ds = (x.cpu().numpy() for x in env.rollout_paired(ref, "cubeful"))
+    dm, ds = (x.cpu().numpy() for x in env.rollout_paired(ref, "cubeful" if match is None else "mwc"))
     h = {k: v.cpu().numpy() for k, v in r.items()}
     T = float(int(trials))
     out = []
@@ -208,14 +228,23 @@ def cube_action(env, states28, turn, cube_value=1, cube_owner=0, trials=1296, ma
              "cubeless": sg * float(h["equity"][p]), "cubeless_stderr": float(h["equity_stderr"][p]),
              "shares": {"win": int(cnt[:3].sum()) / T, "win_gammon": int(cnt[1:3].sum()) / T, "win_backgammon": int(cnt[2]) / T,
                         "lose": int(cnt[3:].sum()) / T, "lose_gammon": int(cnt[4:].sum()) / T, "lose_backgammon": int(cnt[5]) / T}}
+        if match is not None:                              # the roller's match-winning chance: PLAYER2 sees 1 - PLAYER1's
+            side = (lambda x: x) if tu[p] == 0 else (lambda x: 1.0 - x)
+            e.update(nd=side(float(h["mwc"][p])), nd_stderr=float(h["mwc_stderr"][p]), mwc=float(h["mwc"][p]))
         if p in dt_of:
             q = dt_of[p]
             d, se = sg * float(dm[q]), float(ds[q])
-            e.update(dt=sg * float(h["cubeful"][q]), dt_stderr=float(h["cubeful_stderr"][q]), dp=float(cv[p]), diff=d, diff_stderr=se,
-                     jsd=0.0 if d == 0.0 else (math.inf if se == 0.0 else abs(d) / se))
+            if match is None:
+                e.update(dt=sg * float(h["cubeful"][q]), dt_stderr=float(h["cubeful_stderr"][q]), dp=float(cv[p]))
+            else:
+                c = int(cv[p])
+                mine, yours = (int(a1[p]), int(a2[p])) if tu[p] == 0 else (int(a2[p]), int(a1[p]))
+                e.update(dt=side(float(h["mwc"][q])), dt_stderr=float(h["mwc_stderr"][q]),
+                         dp=match.table.after(mine - c, yours, int(ms[p])))      # W(c) from the roller's own row, as the thresholds read it
+            e.update(diff=d, diff_stderr=se, jsd=0.0 if d == 0.0 else (math.inf if se == 0.0 else abs(d) / se))
             e["action"] = cube_decision(e["nd"], e["dt"], e["dp"])
         else:
-            e["action"] = "game over" if over[p] else "no access"
+            e["action"] = "game over" if over[p] else label.get(p, "no access")
         out.append(e)
     return out
 

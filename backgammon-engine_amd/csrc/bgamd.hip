@@ -51,6 +51,8 @@ constexpr bool EXPERIMENTAL_BUILD = false;
 #include "bg_staged.h"
 #include "bg_search3.h"
 #include "bg_cube.h"
+#include "bg_match.h"
+#include "bg_match_plan.h"
 
 using namespace bg;
 
@@ -804,6 +806,7 @@ struct RolloutResult {
     cube::Rule cube_rule{};                // cube: the rule it was played under
     int64_t info[4] = {0, 0, 0, 0};        // bgamd_env_rollout_info
     int64_t cube_info[2] = {0, 0};         // bgamd_env_rollout_cube_info
+    bool match = false;                    // it ran under a match (bgamd_env_rollout_match) whose tables are still the uploaded ones
 };
 
 // Monte Carlo rollouts (bgamd_env_rollout, bg_rollout.h), and what the luck-adjusted ones add (bg_vr.h)
@@ -827,6 +830,11 @@ struct RolloutState {
     uint32_t *cstart = nullptr;
     unsigned long long *cctr = nullptr;
     long long cap_ctrials = 0, cap_cstart = 0;
+    // match play (bgamd_env_rollout_match, bg_match.h): mwords [cap_mwords] the positions' packed (away1, away2, state), cmwc [cap_mtrials]
+    // the trials' MWC (left by the reduce launch that ends a rollout under a match: bgamd_env_rollout_paired_read's which = 4)
+    uint32_t *mwords = nullptr;
+    double *cmwc = nullptr;
+    long long cap_mwords = 0, cap_mtrials = 0;
     RolloutResult last;
 };
 static_assert(cube::LANE_FINISHED == META_FINISHED && cube::LANE_NONE == RO_NONE && cube::WORD_TRUNC == RO_TRUNC &&
@@ -892,6 +900,13 @@ struct bgamd_env {
     int cube_flags = 0;
     cube::Rule cube_rule{0.70, 0.78, 1.0, 64u, 0, 0};
     const int32_t *cube_value = nullptr, *cube_owner = nullptr;
+    // bgamd_env_rollout_match: the sticky match setting (flags 0 = off), the uploaded block (bg_match_plan.h, Layout) and the caller's
+    // score tables, read by the next rollout's intake
+    int match_flags = 0;
+    double *match_blob[2] = {nullptr, nullptr};        // two blocks of the largest layout each: a setting is written into the one not in
+    int match_cur = 0;                                 // force (match_cur) and put in force only once it is whole
+    match::Table match_tab{};
+    const int32_t *match_away1 = nullptr, *match_away2 = nullptr, *match_state = nullptr;
     AnalysisState ana;
     RolloutState ro;
     PrerollState pre;
@@ -2321,6 +2336,7 @@ struct RolloutCall {
     bgamd_env *sc = nullptr;               // the trial env: env->rscratch, exactly p.L lanes
     RoView r{};
     long long steps = 0;                   // env steps issued on the trial env (bgamd_env_rollout_info [1])
+    bool match = false;                    // a match is set (bg_match.h): its init and turn kernels stand in for the cube's
 
     // the scratch env (exactly L lanes) and the buffers of this call: one pass over the plan's needs (a need of 0 grows nothing)
     int buffers()
@@ -2341,6 +2357,9 @@ struct RolloutCall {
             (rc = mem.grow(n.ctrials, ro.cap_ctrials, {BG_BUF(ro.ctrial, sizeof(cube::Trial)), BG_BUF(ro.ceq, 8)})) ||
             (rc = mem.grow(n.cstart, ro.cap_cstart, {BG_BUF(ro.cstart, 2 * 4)})))
             return rc;
+        const match::Needs mn = match::needs(match, p.P, p.N);
+        if ((rc = mem.grow(mn.words, ro.cap_mwords, {BG_BUF(ro.mwords, 4)})) || (rc = mem.grow(mn.trials, ro.cap_mtrials, {BG_BUF(ro.cmwc, 8)})))
+            return rc;
         if (p.cube && !ro.cctr && (rc = mem.alloc(BG_BUF(ro.cctr, cube::CTR_WORDS * 8)))) return rc;
         if (!ro.host && (rc = mem.alloc_pinned(BG_BUF(ro.host, 8 * 8)))) return rc;        // the pinned words and the two events: first use
         for (hipEvent_t &e : ro.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -2355,8 +2374,10 @@ struct RolloutCall {
         unsigned long long intake = 0;
         if (p.grouped) hipLaunchKernelGGL(ro_group_intake_kernel<128>, grid1(p.P, 128), dim3(128), 0, s, d_group, p.P, p.T, ro.group, &env->a_ctr[A_INTAKE]);
         if (p.cube) cube::intake(s, p.P, env->cube_value, env->cube_owner, ro.cstart, &env->a_ctr[A_INTAKE], (unsigned long long)ERRF_RO_CUBE);
+        if (match) match::intake(s, p.P, env->match_tab.M, env->match_away1, env->match_away2, env->match_state, ro.mwords, &env->a_ctr[A_INTAKE],
+                                 match::ERRF_RO_MATCH);
         const int rc = intake_positions(env, d_states28, d_turn, p.P, ro.pos, s, &intake);
-        if (intake & (ERRF_RO_GROUP | ERRF_RO_CUBE)) return BGAMD_E_INVALID;
+        if (intake & (ERRF_RO_GROUP | ERRF_RO_CUBE | match::ERRF_RO_MATCH)) return BGAMD_E_INVALID;
         return rc;
     }
     // trial jl = p T + i of the call plays game id base + jl (base = position_offset T): episode jl + L - g of lane g, stride 1.
@@ -2402,7 +2423,8 @@ struct RolloutCall {
         // the cube: every trial's record at its start, with the decision before a rotated turn 0 on the position's own mean
         if (p.cube) {
             HIPCHK(hipMemsetAsync(ro.cctr, 0, cube::CTR_WORDS * 8, s));
-            cube::init(s, p.N, p.T, p.rotate ? 1 : 0, ro.pos, ro.cstart, p.P, ro.m0, env->cube_rule, ro.ctrial);
+            if (match) match::init(s, p.N, p.T, p.rotate ? 1 : 0, ro.pos, ro.cstart, p.P, ro.m0, env->cube_rule, env->match_tab, ro.mwords, ro.ctrial);
+            else cube::init(s, p.N, p.T, p.rotate ? 1 : 0, ro.pos, ro.cstart, p.P, ro.m0, env->cube_rule, ro.ctrial);
         }
         HIPCHK(hipGetLastError());
         return BGAMD_OK;
@@ -2412,7 +2434,8 @@ struct RolloutCall {
     {
         if (const int e = preroll_pass(env, p.slot, p.L, nullptr, &sc->v, ro.vf, s)) return e;
         hipLaunchKernelGGL(ro_vr_luck_kernel, grid1(p.L, RO_NT), dim3(RO_NT), 0, s, sc->v, (const uint32_t *)ro.lane, (const float *)ro.vf, ro.tluck);
-        if (p.cube) cube::turn(s, p.L, sc->v.meta, sc->v.ply, ro.lane, ro.vf, env->cube_rule, ro.ctrial, ro.cctr);
+        if (match) match::turn(s, p.L, p.T, sc->v.meta, sc->v.ply, ro.lane, ro.vf, env->cube_rule, env->match_tab, ro.mwords, ro.ctrial, ro.cctr);
+        else if (p.cube) cube::turn(s, p.L, sc->v.meta, sc->v.ply, ro.lane, ro.vf, env->cube_rule, ro.ctrial, ro.cctr);
         return BGAMD_OK;
     }
     int refill()
@@ -2497,11 +2520,14 @@ struct RolloutCall {
             cube::reduce(s, p.P, p.T, ro.tval, ro.tturns, ro.ctrial, env->cube_rule, ro.ceq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
             HIPCHK(hipMemcpyAsync(h_cube, ro.cctr, sizeof h_cube, hipMemcpyDeviceToHost, s));
         }
+        // a match: every trial's MWC into the env's buffer (the paired read's which = 4)
+        if (match) match::reduce(s, p.P, p.T, ro.tval, ro.tturns, ro.ctrial, env->match_tab, ro.mwords, ro.cmwc, nullptr, nullptr, nullptr, nullptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
         RolloutResult done{true, p.vr, p.cube, p.grouped, p.P, p.T, env->cube_rule, {p.L, steps, (int64_t)h[4], p.R},
                            {(int64_t)h_cube[cube::CTR_TURNS], (int64_t)h_cube[cube::CTR_AFTER_DROP]}};
         if (!p.cube) for (int k = 0; k < 2; ++k) done.cube_info[k] = ro.last.cube_info[k];     // (still those of the last call that had the cube)
+        done.match = match;
         ro.last = done;
         return BGAMD_OK;
     }
@@ -2530,8 +2556,11 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
                                                          d_group != nullptr, env->ro_plies, env->ro_top_k, (env->cube_flags & BGAMD_CUBE_ON) != 0,
                                                          {env->net.has_weights[0], env->net.has_weights[1]}}, RO_TURN_LIMIT);
     if (plan.rc) return plan.rc;
+    const bool match_on = (env->match_flags & BGAMD_MATCH_ON) != 0;
+    if (match::check_call(match_on, env->cube_flags, flags) != match::CALL_OK) return BGAMD_E_INVALID;
     HIPCHK(hipSetDevice(env->device));
     RolloutCall call{env, plan, (hipStream_t)stream, env->ro};
+    call.match = match_on;
     int rc;
     if ((rc = call.buffers()) || (rc = call.intake(d_states28, d_turn, d_group)) || (rc = call.seat(seed)) ||
         (rc = call.fan()) || (rc = call.luck_init()) || (rc = call.play()))        // turn 0 (the rotation fan, the luck and cube records), then the trials
@@ -2544,12 +2573,18 @@ int bgamd_env_rollout_paired_read(bgamd_env *env, const int32_t *d_ref, int whic
     ENV_GUARD(env);
     const RolloutState &ro = env->ro;
     const RolloutResult &last = ro.last;
-    if (!last.ok || !d_ref || which < 0 || which > 3) return BGAMD_E_INVALID;
+    if (!last.ok || !d_ref || which < 0 || which > 4) return BGAMD_E_INVALID;
     if (which == 1 && !last.vr) return BGAMD_E_INVALID;
     const int32_t *group = last.grouped ? (const int32_t *)ro.group : (const int32_t *)nullptr;
     if (which == 3) {                                  // the cubeful equity: the buffer the cubeful rollout's reduce launch left (bg_cube.h)
         if (!last.cube) return BGAMD_E_INVALID;
         cube::paired((hipStream_t)stream, last.P, last.T, d_ref, group, ro.ceq, d_diff_mean, d_diff_stderr);
+        HIPCHK(hipGetLastError());
+        return BGAMD_OK;
+    }
+    if (which == 4) {                                  // the MWC: the buffer the reduce launch of a rollout under a match left (bg_match.h)
+        if (!last.match) return BGAMD_E_INVALID;
+        cube::paired((hipStream_t)stream, last.P, last.T, d_ref, group, ro.cmwc, d_diff_mean, d_diff_stderr);
         HIPCHK(hipGetLastError());
         return BGAMD_OK;
     }
@@ -2603,6 +2638,63 @@ int bgamd_env_rollout_cube_info(bgamd_env *env, int64_t h_out[2])
 {
     if (!env || !h_out) return BGAMD_E_INVALID;
     h_out[0] = env->ro.last.cube_info[0]; h_out[1] = env->ro.last.cube_info[1];
+    return BGAMD_OK;
+}
+
+// ---- match play on the cubeful rollouts (bg_match.h, bg_match_plan.h) ------------------------------------------------------------------
+int bgamd_env_rollout_match(bgamd_env *env, int match_flags, int64_t M, const double *h_met, const double *h_met_pc, double window_share,
+                            const int32_t *d_away1, const int32_t *d_away2, const int32_t *d_state)
+{
+    if (!env || (match_flags & ~BGAMD_MATCH_ON)) return BGAMD_E_INVALID;
+    if (!(match_flags & BGAMD_MATCH_ON)) {             // off: the rollouts launch what they did before
+        env->match_flags = 0; env->match_away1 = env->match_away2 = env->match_state = nullptr;
+        return BGAMD_OK;
+    }
+    if (match::check_setting(match_flags, M, h_met, h_met_pc, window_share) != match::SET_OK || !d_away1 || !d_away2 || !d_state)
+        return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    const match::Layout l = match::layout((int)M);
+    const std::vector<double> blob = match::build((int)M, h_met, h_met_pc, window_share);
+    // Everything that can fail comes first and touches nothing in force: the two blocks (first use), the wait for stream-ordered readers,
+    // the copy into the block that is NOT in force.  Only then is the setting changed, in plain assignments.
+    if (!env->match_blob[0]) {
+        const size_t bytes = (size_t)match::layout(match::MAX_POINTS).doubles * 8;
+        if (const int rc = env->mem.alloc_group({BG_BUF(env->match_blob[0], bytes), BG_BUF(env->match_blob[1], bytes)})) return rc;
+    }
+    HIPCHK(hipDeviceSynchronize());
+    double *dst = env->match_blob[env->match_cur ^ 1];
+    HIPCHK(hipMemcpy(dst, blob.data(), (size_t)l.doubles * 8, hipMemcpyHostToDevice));
+    env->match_cur ^= 1;
+    env->match_tab = match::Table{dst + l.met, dst + l.met_pc, reinterpret_cast<const double2 *>(dst + l.thr), l.M, l.levels};
+    env->ro.last.match = false;                        // (a rollout that ran under the old tables can no longer be read as a match)
+    env->match_flags = match_flags;
+    env->match_away1 = d_away1; env->match_away2 = d_away2; env->match_state = d_state;
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_match_results(bgamd_env *env, double *d_mwc, double *d_mwc_stderr, int64_t *d_counts, double *d_trial_mwc, void *stream)
+{
+    ENV_GUARD(env);
+    const RolloutState &ro = env->ro;
+    if (!ro.last.ok || !ro.last.match) return BGAMD_E_INVALID;
+    match::reduce((hipStream_t)stream, ro.last.P, ro.last.T, ro.tval, ro.tturns, ro.ctrial, env->match_tab, ro.mwords, ro.cmwc, d_mwc, d_mwc_stderr,
+                  d_counts, d_trial_mwc);
+    HIPCHK(hipGetLastError());
+    return BGAMD_OK;
+}
+
+int bgamd_env_rollout_match_thresholds(bgamd_env *env, int state, int64_t cube, int a, int b, double h_out[2])
+{
+    if (!env || !h_out || !env->match_tab.thr) return BGAMD_E_INVALID;
+    const match::Table &t = env->match_tab;
+    if ((state != match::NORMAL && state != match::POST_CRAWFORD) || cube < 1 || (cube & (cube - 1)) || a < 1 || a > t.M || b < 1 || b > t.M)
+        return BGAMD_E_INVALID;
+    int level = 0;
+    while ((1ll << level) < cube) ++level;
+    if (level >= t.levels) return BGAMD_E_INVALID;
+    HIPCHK(hipSetDevice(env->device));
+    const match::Layout l = match::layout(t.M);
+    HIPCHK(hipMemcpy(h_out, t.thr + match::thr_index(l, state, level, a, b), 16, hipMemcpyDeviceToHost));
     return BGAMD_OK;
 }
 

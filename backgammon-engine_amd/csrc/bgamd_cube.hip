@@ -7,6 +7,7 @@
 
 #include "bg_board.h"
 #include "bg_cube.h"
+#include "bg_match.h"
 
 using namespace bg;
 using bg::cube::Rule;
@@ -220,6 +221,192 @@ __global__ __launch_bounds__(NT) void ro_cube_pair_kernel(long long P, long long
     }
 }
 
+// ---- match play (bg_match.h): the cube's init and turn with a match score's conditions and thresholds; a trial's worth as an MWC ------
+using bg::match::Table;
+
+// the fields of a position's word
+__device__ __forceinline__ uint32_t match_away(uint32_t word, int side) { return (word >> (side ? 8 : 0)) & 0xFFu; }
+__device__ __forceinline__ uint32_t match_state(uint32_t word) { return (word >> 16) & 3u; }
+
+// after(a1, a2, state) of bg_match.h: the MWC of the side needing a1.  a1, a2 <= M whenever the table is read.
+__device__ __forceinline__ double match_after(long long a1, long long a2, uint32_t state, const Table &tab)
+{
+    if (a1 <= 0) return 1.0;
+    if (a2 <= 0) return 0.0;
+    if (state != 0u && a2 == 1) return tab.met_pc[a1 - 1];
+    if (state != 0u && a1 == 1) return __dsub_rn(1.0, tab.met_pc[a2 - 1]);
+    return tab.met[(a1 - 1) * tab.M + (a2 - 1)];
+}
+
+// cube_offer under a match: no decision in the Crawford game or on a dead cube (c >= the roller's away: the trial is marked); else the
+// table's entry for (state, c, roller's away, opponent's away) in the place of the call's double_at and pass_at.  -> the record changed
+__device__ __forceinline__ bool match_offer(Trial &t, int mover, double mean, uint32_t k, const Rule &r, const Table &tab, uint32_t word)
+{
+    const uint32_t owner = t.info & cube::INFO_OWNER;
+    if (t.dropped >= 0 || t.value >= r.max_cube || !(owner == 0u || owner == (uint32_t)mover + 1u)) return false;
+    const uint32_t st = match_state(word);
+    if (st == 1u) return false;
+    const uint32_t a = match_away(word, mover), b = match_away(word, mover ^ 1);
+    if (t.value >= a) {
+        if (t.spare & match::TRIAL_DEAD) return false;
+        t.spare |= match::TRIAL_DEAD;
+        return true;
+    }
+    const int level = __ffs((int)t.value) - 1;         // (t.value < a <= M: level < levels)
+    const double2 th = tab.thr[(((long long)(st ? 1 : 0) * tab.levels + level) * tab.M + (a - 1u)) * tab.M + (b - 1u)];
+    const double w = mover ? 1.0 - mean : mean;
+    if (!(th.x <= w && w <= r.too_good_at)) return false;
+    const uint32_t opp = 2u - (uint32_t)mover;
+    if (w > th.y) {
+        t.dropped = (int32_t)k;
+        t.info |= opp << cube::INFO_PASSED_SHIFT;
+    } else {
+        t.value *= 2u;
+        t.info = ((t.info & ~cube::INFO_OWNER) | opp) + (1u << cube::INFO_TURNS_SHIFT);
+    }
+    return true;
+}
+
+// thread per position: the caller's score tables into one word each; away outside 1 .. M, a state outside 0 .. 2, or a state that does
+// not go with the score (1 and 2 iff a side is 1-away) sets err_bit in the intake word, and the word is that of a Crawford game at 1-1
+template <int NT>
+__global__ __launch_bounds__(NT) void ro_match_intake_kernel(long long P, int M, const int32_t *__restrict__ d_away1,
+                                                             const int32_t *__restrict__ d_away2, const int32_t *__restrict__ d_state,
+                                                             uint32_t *__restrict__ words, unsigned long long *err, unsigned long long err_bit)
+{
+    const long long p = (long long)blockIdx.x * NT + threadIdx.x;
+    if (p >= P) return;
+    const int32_t a1 = d_away1[p], a2 = d_away2[p], st = d_state[p];
+    bool bad = a1 < 1 || a1 > M || a2 < 1 || a2 > M || st < 0 || st > 2;
+    if (!bad) bad = ((a1 < a2 ? a1 : a2) == 1) != (st != 0);
+    if (bad) atomicOr(err, err_bit);
+    words[p] = bad ? (1u | 1u << 8 | 1u << 16) : ((uint32_t)a1 | (uint32_t)a2 << 8 | (uint32_t)st << 16);
+}
+
+// ro_cube_init_kernel under a match
+template <int NT>
+__global__ __launch_bounds__(NT) void ro_match_init_kernel(long long N, long long T, int rotate, const uint4 *__restrict__ pos_rows,
+                                                           const uint32_t *__restrict__ start, long long P, const double *__restrict__ mean0,
+                                                           Rule rule, Table tab, const uint32_t *__restrict__ words, Trial *__restrict__ trials)
+{
+    const long long jl = (long long)blockIdx.x * NT + threadIdx.x;
+    if (jl >= N) return;
+    const long long pi = jl / T;
+    Trial t{start[pi], -1, start[P + pi], 0u};
+    if (rotate && !rule.hold_turn0) {
+        const uint4 a = pos_rows[2 * pi], b = pos_rows[2 * pi + 1];
+        const uint32_t p[8] = {a.x & ~TURN_BIT, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        if (!over_code(p)) match_offer(t, (a.x & TURN_BIT) ? 1 : 0, mean0[pi], 0u, rule, tab, words[pi]);
+    }
+    *reinterpret_cast<uint4 *>(trials + jl) = make_uint4(t.value, (uint32_t)t.dropped, t.info, t.spare);
+}
+
+// ro_cube_turn_kernel under a match: trial j belongs to position j / T
+template <int NT>
+__global__ __launch_bounds__(NT) void ro_match_turn_kernel(long long L, uint32_t T, const uint32_t *__restrict__ meta,
+                                                           const uint32_t *__restrict__ ply, const uint32_t *__restrict__ lane_trial,
+                                                           const float *__restrict__ f, Rule rule, Table tab, const uint32_t *__restrict__ words,
+                                                           Trial *__restrict__ trials, unsigned long long *__restrict__ ctr)
+{
+    const long long g = (long long)blockIdx.x * NT + threadIdx.x;
+    bool live = false, after = false;
+    if (g < L) {
+        const uint32_t m = meta[g], j = lane_trial[g];
+        live = !(m & cube::LANE_FINISHED) && j != cube::LANE_NONE;
+        if (live) {
+            const uint4 w = *reinterpret_cast<const uint4 *>(trials + j);
+            Trial t{w.x, (int32_t)w.y, w.z, w.w};
+            const uint32_t k = ply[g];
+            if (t.dropped < 0 && !(rule.hold_turn0 && k == 0u) &&
+                match_offer(t, (int)(m & 1u), cube_pre_mean(f + g * cube::ROLLS), k, rule, tab, words[j / T]))
+                *reinterpret_cast<uint4 *>(trials + j) = make_uint4(t.value, (uint32_t)t.dropped, t.info, t.spare);
+            after = t.dropped >= 0;
+        }
+    }
+    const unsigned long long nl = (unsigned long long)__popcll(__ballot(live)), na = (unsigned long long)__popcll(__ballot(after));
+    if ((threadIdx.x & 63) == 0) {
+        if (nl) atomicAdd(&ctr[cube::CTR_TURNS], nl);
+        if (na) atomicAdd(&ctr[cube::CTR_AFTER_DROP], na);
+    }
+}
+
+// PLAYER1's MWC of a trial (bg_match.h); ended: +1 the trial ended the match for PLAYER1, -1 for PLAYER2, 0 neither (or truncated)
+__device__ __forceinline__ double match_mwc(const Trial &t, float x, uint32_t word_t, uint32_t word_p, const Table &tab, int &ended)
+{
+    // (the compiler contracts a product and a sum into a fused multiply-add unless told otherwise, through __dmul_rn / __dadd_rn too,
+    // which are a plain product and sum to it: the truncated payoff, the one place of the rule where that would change a bit, is
+    // written with operators under this pragma)
+#pragma clang fp contract(off)
+    const long long c = (long long)t.value, a1 = (long long)match_away(word_p, 0), a2 = (long long)match_away(word_p, 1);
+    const uint32_t st = match_state(word_p);
+    long long r;
+    if (t.dropped >= 0) r = ((t.info >> cube::INFO_PASSED_SHIFT) & 3u) == 2u ? c : -c;
+    else {
+        const int pts = (int)(word_t << (29 - cube::WORD_PTS_SHIFT)) >> 29;
+        if (pts == 0) {
+            ended = 0;
+            const double xd = (double)x;
+            const double won = xd * match_after(a1 - c, a2, st, tab), lost = (1.0 - xd) * match_after(a1, a2 - c, st, tab);
+            return won + lost;                         // (dadd(dmul(x, .), dmul(dsub(1, x), .)): three roundings, by the pragma above)
+        }
+        r = c * (long long)pts;
+    }
+    const long long b1 = a1 - (r > 0 ? r : 0), b2 = a2 - (r < 0 ? -r : 0);
+    ended = b1 <= 0 ? 1 : (b2 <= 0 ? -1 : 0);
+    return match_after(b1, b2, st, tab);
+}
+
+// ro_cube_reduce_kernel's two passes and butterfly on the trials' MWC.  counts[p][3]: trials that ended the match for PLAYER1, for
+// PLAYER2, trials in which some decision was withheld by a dead cube.
+template <int NT>
+__global__ __launch_bounds__(NT) void ro_match_reduce_kernel(long long T, const float *__restrict__ t_val, const uint32_t *__restrict__ t_turns,
+                                                             const Trial *__restrict__ trials, Table tab, const uint32_t *__restrict__ words,
+                                                             double *__restrict__ t_mwc, double *__restrict__ mean, double *__restrict__ serr,
+                                                             int64_t *__restrict__ counts, double *__restrict__ o_mwc)
+{
+    // (no product is contracted with a sum in here: the sum of squares is the chain of rounded products and sums a host restates)
+#pragma clang fp contract(off)
+    static_assert(NT == 64, "one wave per position");
+    const long long p = blockIdx.x, base = p * T;
+    const int lane = threadIdx.x;
+    const uint32_t word_p = words[p];
+    double s = 0.0;
+    unsigned long long c[3] = {0ull, 0ull, 0ull};
+    for (long long i = lane; i < T; i += 64) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(trials + base + i);
+        const Trial t{w.x, (int32_t)w.y, w.z, w.w};
+        int ended;
+        const double e = match_mwc(t, t_val[base + i], t_turns[base + i], word_p, tab, ended);
+        s = __dadd_rn(s, e);
+        c[0] += ended > 0 ? 1ull : 0ull;
+        c[1] += ended < 0 ? 1ull : 0ull;
+        c[2] += (t.spare & match::TRIAL_DEAD) ? 1ull : 0ull;
+        t_mwc[base + i] = e;
+        if (o_mwc) o_mwc[base + i] = e;
+    }
+    const double m = cube_wave_sum(s) / (double)T;
+    double q = 0.0;
+    for (long long i = lane; i < T; i += 64) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(trials + base + i);
+        const Trial t{w.x, (int32_t)w.y, w.z, w.w};
+        int ended;
+        const double d = match_mwc(t, t_val[base + i], t_turns[base + i], word_p, tab, ended) - m;
+        const double dd = d * d;
+        q = q + dd;
+    }
+    q = cube_wave_sum(q);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = cube_wave_sum_u64(c[k]);
+    if (lane == 0) {
+        if (mean) mean[p] = m;
+        if (serr) serr[p] = T > 1 ? sqrt(q / ((double)T * (double)(T - 1))) : 0.0;
+        if (counts) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) counts[p * 3 + k] = (int64_t)c[k];
+        }
+    }
+}
+
 }  // namespace
 
 // ---- the launches (bg_cube.h) ---------------------------------------------------------------------------------------------------------
@@ -255,4 +442,34 @@ void paired(hipStream_t s, long long P, long long T, const int32_t *ref, const i
 }
 
 }  // namespace cube
+
+// ---- the launches (bg_match.h) --------------------------------------------------------------------------------------------------------
+namespace match {
+static dim3 grid1(long long n, int bs) { return dim3((unsigned)((n + bs - 1) / bs)); }
+
+void intake(hipStream_t s, long long P, int M, const int32_t *d_away1, const int32_t *d_away2, const int32_t *d_state, uint32_t *words,
+            unsigned long long *err_word, unsigned long long err_bit)
+{
+    hipLaunchKernelGGL(ro_match_intake_kernel<128>, grid1(P, 128), dim3(128), 0, s, P, M, d_away1, d_away2, d_state, words, err_word, err_bit);
+}
+void init(hipStream_t s, long long N, long long T, int rotate, const uint4 *pos_rows, const uint32_t *start, long long P, const double *mean0,
+          cube::Rule rule, Table tab, const uint32_t *words, cube::Trial *trials)
+{
+    hipLaunchKernelGGL(ro_match_init_kernel<CUBE_NT>, grid1(N, CUBE_NT), dim3(CUBE_NT), 0, s, N, T, rotate, pos_rows, start, P, mean0, rule, tab,
+                       words, trials);
+}
+void turn(hipStream_t s, long long L, long long T, const uint32_t *meta, const uint32_t *ply, const uint32_t *lane_trial, const float *f,
+          cube::Rule rule, Table tab, const uint32_t *words, cube::Trial *trials, unsigned long long *ctr)
+{
+    hipLaunchKernelGGL(ro_match_turn_kernel<CUBE_NT>, grid1(L, CUBE_NT), dim3(CUBE_NT), 0, s, L, (uint32_t)T, meta, ply, lane_trial, f, rule, tab,
+                       words, trials, ctr);
+}
+void reduce(hipStream_t s, long long P, long long T, const float *t_val, const uint32_t *t_turns, const cube::Trial *trials, Table tab,
+            const uint32_t *words, double *t_mwc, double *mean, double *serr, int64_t *counts, double *o_mwc)
+{
+    hipLaunchKernelGGL(ro_match_reduce_kernel<64>, dim3((unsigned)P), dim3(64), 0, s, T, t_val, t_turns, trials, tab, words, t_mwc, mean, serr,
+                       counts, o_mwc);
+}
+
+}  // namespace match
 }  // namespace bg

@@ -484,7 +484,8 @@ int bgamd_env_rollout_grouped(bgamd_env *env, int flags, const int32_t *d_states
 /* Paired differences of the last rollout of either kind (P and T of that call; BGAMD_E_INVALID before the first or after one that failed).
  * `which` selects the per-trial quantity q: 0 the value x_i; 1 the luck-adjusted y_i = (double) x_i - L_i (BGAMD_E_INVALID unless that
  * rollout had BGAMD_ROLLOUT_VR); 2 the equity e_i in points as bgamd_env_rollout_outcomes_read defines it; 3 the cubeful
- * equity of bgamd_env_rollout_cube_read (BGAMD_E_INVALID unless that rollout ran with the cube on).  Other values: BGAMD_E_INVALID.
+ * equity of bgamd_env_rollout_cube_read (BGAMD_E_INVALID unless that rollout ran with the cube on); 4 the match-winning chance of
+ * bgamd_env_rollout_match_results (BGAMD_E_INVALID unless that rollout ran under a match).  Other values: BGAMD_E_INVALID.
  * For each position p with its reference r = d_ref[p], in fp64:
  *   d_i = q_i(p) - q_i(r);  d_diff_mean[p] = (1/T) sum d_i;  d_diff_stderr[p] = sqrt(sum (d_i - diff_mean)^2 / (T (T - 1))), 0 for T = 1,
  * reduced in the fixed order of the plain statistics (one wave per position, lane k takes trials k, k + 64, ..., then the same butterfly).
@@ -612,8 +613,8 @@ int bgamd_env_rollout_outcomes_read(bgamd_env *env, int64_t *d_counts, double *d
  * no power of two in 1 .. 2^30, or an owner outside 0 .. 2, is refused (BGAMD_E_INVALID) in the pass that refuses bad states.  The plain
  * outputs, bgamd_env_rollout_info, bgamd_env_rollout_vr_read, bgamd_env_rollout_outcomes_read and bgamd_env_rollout_paired_read with
  * which 0 .. 2 are bit for bit what the same call without the cube returns.
- * Out of scope: the cube in live envs, self-play and the arena; match play; cube-aware checker play; freeing a lane at a drop; cubeful
- * rollouts without the luck pass. */
+ * Out of scope: the cube in live envs, self-play and the arena; cube-aware checker play; freeing a lane at a drop; cubeful rollouts
+ * without the luck pass.  (Match play: bgamd_env_rollout_match below.) */
 enum { BGAMD_CUBE_ON = 1, BGAMD_CUBE_JACOBY = 2, BGAMD_CUBE_HOLD_TURN0 = 4 };
 int bgamd_env_rollout_cube(bgamd_env *env, int cube_flags, double double_at, double pass_at, double too_good_at, int64_t max_cube,
                            const int32_t *d_cube_value /*[P]*/, const int32_t *d_cube_owner /*[P]*/);
@@ -630,6 +631,70 @@ int bgamd_env_rollout_cube_read(bgamd_env *env, double *d_cubeful, double *d_cub
  * ordered pair), those of them played after the trial's drop, the turn the drop is made before included].  h_out[1] / h_out[0] is the
  * share of the rollout's work that freeing a lane at a drop would save. */
 int bgamd_env_rollout_cube_info(bgamd_env *env, int64_t h_out[2]);
+
+/* ---- match play on the cubeful rollouts: match-winning chance by score ------------------------------------------------------------------
+ * At a match score the cube's thresholds stop being constants, some cubes are dead, the Crawford game has no cube, and a trial is worth
+ * a match-winning chance (MWC), not points.  A match is a second sticky setting on top of bgamd_env_rollout_cube: the same trials, the
+ * same per-trial record with its one writer, the cube's conditions and four of its settings (too_good_at, max_cube, the start tables,
+ * BGAMD_CUBE_HOLD_TURN0); the cube setting's double_at and pass_at are IGNORED while a match is set.  All arithmetic is fp64 and every
+ * operation is rounded on its own (no fused multiply-add, on the device or on the host), so a Python float model is exact.
+ * A SETTING: a table size M, 1 <= M <= 64; met[M][M], met[a-1][b-1] = the chance that a side needing a points beats a side needing b,
+ * the 1-away row and column holding the Crawford-game values; met_pc[M], met_pc[k-1] = the post-Crawford chance of a trailer needing k
+ * against a leader needing 1 (met_pc[0]: double match point); window_share in [0, 1].  Per position p: away1[p], away2[p] in 1 .. M
+ * (PLAYER1's and PLAYER2's points to go) and state[p]: 0 normal, 1 the Crawford game, 2 post-Crawford; 1 and 2 are valid iff
+ * min(away1, away2) == 1, 0 iff min(away1, away2) > 1.
+ * after(a1, a2, state) is the MWC of the side needing a1 when the next game starts against a side needing a2; the first case that
+ * applies:  a1 <= 0: 1.0;  a2 <= 0: 0.0;  state != 0 (the next game is post-Crawford) and a2 == 1: met_pc[a1-1];  state != 0 and
+ * a1 == 1: 1.0 - met_pc[a2-1];  otherwise met[a1-1][a2-1].  Points are subtracted in 64-bit integers (c x 3 can exceed 32 bits).
+ * THE DECISION before turn k.  The cube record's conditions stay (not dropped, position not over, c < max_cube, access to the cube,
+ * BGAMD_CUBE_HOLD_TURN0), and a match adds two: state[p] == 1 (the Crawford game): no decision; c >= the roller's away (a dead cube):
+ * no decision, and the trial is counted as one in which a decision was withheld by a dead cube.  Otherwise, with a the roller's points
+ * to go, b the opponent's, W(k) = after(a - k, b, state) the roller's MWC after winning k points in this game and
+ * L(k) = after(a, b - k, state) after losing k -- the roller reads the table from ITS OWN row, whichever seat it has (for a table with
+ * met[a][b] + met[b][a] == 1 that is 1 - PLAYER1's view up to rounding) -- and W1 = W(c), L1 = L(c), W2 = W(2c), L2 = L(2c):
+ *   pass_at   = (W1 - L2) / (W2 - L2)                         the opponent's dead-cube take point, in the roller's w;
+ *   open      = (L1 - L2) / ((L1 - L2) + (W2 - W1))           where doubling stops losing;
+ *   double_at = open + window_share * (pass_at - open).
+ * A denominator <= 0, or a result that is not finite: no decision is made at that entry (double_at = +inf).  From there the cube's own
+ * rule applies with these two numbers: the roller doubles iff double_at <= w && w <= too_good_at, the opponent passes iff w > pass_at,
+ * and otherwise takes.  The thresholds are computed ONCE per setting on the host, for every (state in {0, 2}, cube 2^l < M, a, b), and
+ * uploaded with the tables: on the device a decision is a few small loads and one 16-byte load, and no division.
+ * The net knows wins only and no gammons, so the thresholds do not either: W(k) and L(k) count single games.  window_share is a rule
+ * of thumb (0.5 is the suggested default) and NO measured optimum, like the cube's own thresholds.
+ * PAYOFF of a trial, PLAYER1's MWC (PLAYER1's row).  r = the trial's points from PLAYER1's side: a dropped trial +-c, c the cube BEFORE
+ * the double; a trial finished on the board c x points; in both cases mwc = after(a1 - max(r, 0), a2 - max(-r, 0), state) -- a gammon
+ * with the cube on 2 at 3-away ends the match, points beyond the match length are worth nothing.  A trial truncated at max_plies with
+ * fp32 value x: mwc = x * after(a1 - c, a2, state) + (1 - x) * after(a1, a2 - c, state), formed as
+ * dadd(dmul(x, .), dmul(dsub(1, x), .)).  Jacoby has no meaning in a match.
+ *
+ * bgamd_env_rollout_match is sticky.  match_flags: BGAMD_MATCH_ON sets it, 0 clears it (the other arguments are ignored; an env that
+ * cleared it behaves as one that never set it).  h_met[M][M] and h_met_pc[M] are HOST pointers, copied at the call together with the
+ * threshold table computed from them.  d_away1, d_away2, d_state are DEVICE pointers [P], read by the next rollout's intake pass like
+ * the cube's start tables; they must stay valid until that call.  Errors (BGAMD_E_INVALID, the setting unchanged): other flags, M
+ * outside 1 .. 64, a NULL table, a table entry outside [0, 1] or not finite, window_share NaN or outside [0, 1].  A call that sets new
+ * tables ends the readability of an earlier rollout as a match (bgamd_env_rollout_match_results, which = 4); clearing does not.
+ * While a match is set: a rollout call with the cube off, with BGAMD_CUBE_JACOBY set, or without BGAMD_ROLLOUT_VR returns
+ * BGAMD_E_INVALID before anything is played; an away outside 1 .. M, a state outside 0 .. 2 or one that does not go with the score is
+ * refused (BGAMD_E_INVALID) in the pass that refuses bad states.  Every other output of the call -- the plain ones,
+ * bgamd_env_rollout_info, the luck and outcome reads, paired which 0 .. 2 -- is bit for bit what it is without the match;
+ * bgamd_env_rollout_cube_read and which = 3 describe, in points, the records the match rule produced.
+ * Out of scope: a match in live envs, self-play and the arena; playing a match game after game; gammon-aware or live-cube thresholds;
+ * automatic doubles and beavers; freeing a lane at a drop; a shipped published match equity table. */
+enum { BGAMD_MATCH_ON = 1 };
+int bgamd_env_rollout_match(bgamd_env *env, int match_flags, int64_t M, const double *h_met /*[M][M]*/, const double *h_met_pc /*[M]*/,
+                            double window_share, const int32_t *d_away1 /*[P]*/, const int32_t *d_away2 /*[P]*/,
+                            const int32_t *d_state /*[P]*/);
+/* The match results of the last rollout, which must have run under a match (else BGAMD_E_INVALID); P and T of that call.  Any pointer
+ * may be NULL.  d_mwc[P], d_mwc_stderr[P] (fp64): mean and standard error of the per-trial MWC of PLAYER1, in the fixed order of
+ * bgamd_env_rollout_cube_read.  d_counts[P][3] (int64): trials that ended the match for PLAYER1, trials that ended it for PLAYER2 (a
+ * truncated trial is in neither), trials in which some decision was withheld by a dead cube.  d_trial_mwc[P][T] (fp64).  Bit for bit
+ * independent of `lanes`, of the call order and of position_offset / group_offset splits.  Stream-ordered. */
+int bgamd_env_rollout_match_results(bgamd_env *env, double *d_mwc, double *d_mwc_stderr, int64_t *d_counts /*[P][3]*/, double *d_trial_mwc,
+                                 void *stream);
+/* h_out = {double_at, pass_at} of the uploaded threshold table, read back from the device: state 0 or 2, cube a power of two below M,
+ * a the roller's and b the opponent's points to go in 1 .. M; +inf, +inf where no decision is made.  BGAMD_E_INVALID for anything else
+ * and before the first setting.  Synchronises. */
+int bgamd_env_rollout_match_thresholds(bgamd_env *env, int state, int64_t cube, int a, int b, double h_out[2]);
 
 /* (slot 8 below counts the 32-row x 2-feature MFMA steps of the dense f32 net, or the W1 columns added by the
  * incremental one) */

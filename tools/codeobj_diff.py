@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Do two builds of the library carry the same gfx950 device code?   tools/codeobj_diff.py OLD.so NEW.so
+"""Do two builds of the library carry the same gfx950 device code?   tools/codeobj_diff.py OLD.so NEW.so [INDEX]
 
 Where a kernel lies in the code object costs about 1 % of the greedy step, so a change that is meant to leave the device
 code alone is checked for exactly that: the .hip_fatbin section of each library is dumped (llvm-objcopy), its gfx950 code object
 unbundled (clang-offload-bundler), and the two objects compared -- the bytes of .text, .rodata and .note, and the address and size of
 every function symbol.  The one difference allowed is the object symbol __hip_cuid_<hash>: its name is a digest of the source.
+INDEX (default 0) picks the translation unit: the library's .hip_fatbin holds one bundle per .hip file in link order (0 bgamd.hip,
+1 bgamd_search3.hip, 2 bgamd_cube.hip).
 Bytes and symbol tables only: nothing is disassembled.  Exit status 0 = identical, 1 = different, 2 = could not compare."""
 import os
 import shutil
@@ -24,10 +26,21 @@ def find_tool(name):
     return shutil.which(name) or shutil.which(name, path=os.pathsep.join(os.path.join(rocm, d) for d in ("llvm/bin", "lib/llvm/bin")))
 
 
-def code_object(lib, workdir, tag):
-    """-> the bytes of lib's gfx950 code object"""
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def code_object(lib, workdir, tag, index=0):
+    """-> the bytes of the gfx950 code object of lib's index-th bundle"""
     fatbin, obj = os.path.join(workdir, tag + ".fatbin"), os.path.join(workdir, tag + ".o")
     subprocess.check_call([find_tool("llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fatbin, lib, os.devnull])
+    if index:
+        with open(fatbin, "rb") as f:
+            blob = f.read()
+        starts = [i for i in range(len(blob)) if blob.startswith(MAGIC, i)]
+        if index >= len(starts):
+            raise OSError("the library holds %d bundles" % len(starts))
+        with open(fatbin, "wb") as f:
+            f.write(blob[starts[index]:starts[index + 1] if index + 1 < len(starts) else len(blob)])
     subprocess.check_call([find_tool("clang-offload-bundler"), "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fatbin,
                            "--output=" + obj])
     with open(obj, "rb") as f:
@@ -86,7 +99,7 @@ def compare(old, new, out=print):
 
 
 def main(argv):
-    if len(argv) != 3:
+    if len(argv) not in (3, 4):
         print(__doc__, file=sys.stderr)
         return 2
     missing = [t for t in TOOLS if not find_tool(t)]
@@ -95,7 +108,8 @@ def main(argv):
         return 2
     with tempfile.TemporaryDirectory() as tmp:
         try:
-            old, new = code_object(argv[1], tmp, "old"), code_object(argv[2], tmp, "new")
+            index = int(argv[3]) if len(argv) == 4 else 0
+            old, new = code_object(argv[1], tmp, "old", index), code_object(argv[2], tmp, "new", index)
         except (OSError, subprocess.CalledProcessError) as e:
             print("could not extract a gfx950 code object: %s" % e, file=sys.stderr)
             return 2

@@ -13,6 +13,10 @@ median ratio; 1 for the plain call).
 cube results read inside the timed region): ms per call with and without the cube, their ratio, and the share of lane-turns played
 after the trial's drop (bgamd_env_rollout_cube_info) -- what not freeing a lane at a drop costs.
 
+--match (with --vr --cube): beside every cube call the same call under a match (bgamd_env_rollout_match: 7-away / 7-away on
+MatchTable.janowski(7), the default window share, the match results read inside the timed region): ms per call, its ratio to the cube
+call, the match's counts, and match_setting_ms: the setting and its clearing alone, which every rollout(match=) call pays.
+
 --outcomes: the same run with the games read in points after every call (bgamd_env_rollout_outcomes_read, inside the timed region):
 every record also carries the six shares (PLAYER1 single game / gammon / backgammon, PLAYER2 the same) over the finished trials of all
 positions and the mean equity of the positions in points.
@@ -80,6 +84,7 @@ def main():
     ap.add_argument("--vr", action="store_true", help="luck-adjusted rollouts against plain ones")
     ap.add_argument("--vr-trials", type=int, default=2592)
     ap.add_argument("--cube", action="store_true", help="--vr: also the same VR calls with the doubling cube on")
+    ap.add_argument("--match", action="store_true", help="--vr --cube: also the same cube calls under a match score")
     ap.add_argument("--outcomes", action="store_true", help="also read gammons / backgammons and the equity in points")
     ap.add_argument("--plies", type=int, default=1, choices=(1, 2), help="who plays the trials: 1 = the greedy step, 2 = the filtered 2-ply search")
     ap.add_argument("--top-k", type=int, default=5, help="--plies 2: the search's top_k")
@@ -93,6 +98,8 @@ def main():
     POLICY = dict(plies=2, top_k=a.top_k, margin=a.margin) if a.plies == 2 else {}
     if a.cube and not a.vr:
         ap.error("--cube rides on the luck pass: give it with --vr")
+    if a.match and not a.cube:
+        ap.error("--match sets the cube's thresholds: give it with --vr --cube")
     if a.vr and a.outcomes:
         ap.error("--outcomes reads the plain run's games; it is not combined with --vr")
     import backgammon_env as bg
@@ -212,13 +219,13 @@ def _groups(bg, w, a):
     print(json.dumps({"rollout_groups_bench": rec}))
 
 
-def _timed(env, st, tu, trials, M, lanes, regions, vr, cube=None):
-    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, cube=cube, **POLICY)      # warm-up
+def _timed(env, st, tu, trials, M, lanes, regions, vr, cube=None, match=None):
+    env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, cube=cube, match=match, **POLICY)      # warm-up
     ms = []
     for _ in range(regions):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, cube=cube, **POLICY)
+        r = env.rollout(st, tu, trials, max_plies=M, rotate=True, seed=5, lanes=lanes, variance_reduction=vr, cube=cube, match=match, **POLICY)
         if cube is not None:
             torch.cuda.synchronize()                               # (the cube read is stream-ordered after the call)
         ms.append((time.perf_counter() - t0) * 1e3)                # (the call synchronises; vr_read is stream-ordered after it)
@@ -260,6 +267,25 @@ def _vr(env, st, tu, a, greedy_sps):
                         "cube_dropped_share": round(float(cc[0] + cc[1]) / n_trials, 4), "cube_turns_per_trial": round(float(cc[2]) / n_trials, 4),
                         "cubeful_mean": round(float(rc["cubeful"].mean()), 5), "cubeless_same_trials_unchanged": bool(
                             torch.equal(rc["mean"], rv["mean"]) and torch.equal(rc["vr_mean"], rv["vr_mean"]))})
+        if a.match:
+            ms_m, rm, mregions = _timed(env, st, tu, a.vr_trials, M, a.lanes, a.regions, True, cube=bg.Cube(),
+                                        match=bg.Match(bg.MatchTable.janowski(7), 7, 7))
+            mc = rm["match_counts"].sum(0).cpu().numpy()
+            # what rollout(match=) pays per call outside the trials: the setting (a device synchronise, the threshold table built on the
+            # host, one synchronous copy) and its clearing -- inside match_ms above, timed here on its own
+            a1 = torch.full((a.positions,), 7, dtype=torch.int32, device=env.device)
+            zero, table, sets = torch.zeros_like(a1), bg.MatchTable.janowski(7), []
+            for _ in range(7):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                env._set_match(table, 0.5, a1, a1, zero)
+                env._lib.bgamd_env_rollout_match(env._h, 0, 0, None, None, 0.0, None, None, None)
+                sets.append((time.perf_counter() - t0) * 1e3)
+            rec["match_setting_ms"] = round(statistics.median(sets), 3)
+            rec.update({"match_ms": round(ms_m, 2), "match_over_cube": round(ms_m / ms_c, 4), "match_regions_ms": [round(x, 2) for x in mregions],
+                        "match_ended_share": round(float(mc[0] + mc[1]) / n_trials, 4), "match_dead_cube_share": round(float(mc[2]) / n_trials, 4),
+                        "mwc_mean": round(float(rm["mwc"].mean()), 5), "cubeless_same_trials_unchanged_by_match": bool(
+                            torch.equal(rm["mean"], rv["mean"]) and torch.equal(rm["vr_mean"], rv["vr_mean"]))})
         print(json.dumps(rec), flush=True)
         out.append(rec)
     print(json.dumps({"rollout_vr_bench": out}))
